@@ -9,6 +9,16 @@ collective: envs are independent, so the batch shards with no data-path exchange
 `--envs` per GPU).  Rank 0 prints one JSON line.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--config rmsc03]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps,
+print the line.  `--full` adds, after the timed steps, the legs that take runs of their own: the
+instrumented batch of the algorithmic-byte count and the `roofline` block built on it, the
+solo-latency run of the latency bound, and the C oracle's `cpu_baseline` (`--no-count`,
+`--no-latency`, `--no-cpu` drop single legs of it).  `--dump-outputs DIR` writes what the last
+timed step left its caller (the gathered episode records, a GymKernel episode's observations and
+flags) as DIR/<name>.npy in float64 / float32, before any `--full` leg runs; the same arguments
+give the same inputs, so two builds compare output for output.
 
 `--gpus N` without a launcher starts N rank processes itself (one per GPU, before anything
 touches a GPU) with the same RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* environment that
@@ -48,14 +58,20 @@ def parse():
                     help="Kernel.runner configurations: a first launch of this many pops, then launches of --chunk "
                          "over the envs still running (mxa_set_launch_schedule); 0 = launches of --chunk only. "
                          "Measured slower for every configuration (DESIGN.md Appendix R.6)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the legs with runs of their own: the counted algorithmic "
+                         "bytes and the roofline block, the latency bound's solo run, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (episode records; GymKernel observations and flags) "
+                         "as DIR/<name>.npy, float64 / float32, at most 64 MB in all")
     ap.add_argument("--cpu-envs", type=int, default=None, help="CPU-baseline sample size (envs)")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="CPU-baseline threads (default: the cores this process may run on, capped by OMP_NUM_THREADS)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--per-step", action="store_true",
                     help="GymKernel configs: one launch per ABIDESEnv.step instead of one per episode")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample: at least this much wall time")
-    ap.add_argument("--no-latency", action="store_true", help="skip the solo-latency run of the latency bound")
+    ap.add_argument("--no-latency", action="store_true", help="--full without the solo-latency run of the latency bound")
     ap.add_argument("--parity-hash", action="store_true",
                     help="also compute the per-pop parity hash (test instrumentation, off by default: "
                          "tests/test_gpu_hash_switch.py shows every market result is identical either way)")
@@ -63,8 +79,8 @@ def parse():
     ap.add_argument("--tape", default=None, help="marketreplay tape under tests/golden (IBM_2003-01-14, GOOG_2012-06-21)")
     ap.add_argument("--stub", action="store_true", help="launcher self-test on CPU/gloo with a synthetic engine")
     ap.add_argument("--no-count", action="store_true",
-                    help="skip the instrumented batch that counts the algorithmic bytes (PMC passes of "
-                         "tools/profile_round.sh: only the timed kernel launches)")
+                    help="--full without the instrumented batch that counts the algorithmic bytes (the roofline "
+                         "block then uses the nominal figure)")
     return ap.parse_args()
 
 
@@ -213,6 +229,44 @@ class Engine:
         return int(e.item())
 
     has_seeds = True
+    return_is_float = False  # record word R_RETURN holds float64 bits (a learner's episode return)
+
+    def outputs(self):
+        """name -> array: what the last step left its caller (--dump-outputs), every array float64
+        or float32.  The gathered episode records go out one column per file; the words that can
+        pass 2**53 (hash, current time in ns) as their exact 32-bit halves."""
+        import numpy as np
+        sh = self.shard
+        g = self.gathered.cpu().numpy()
+        out = {}
+        for name, w in (("events", sh.R_EVENTS), ("status", sh.R_STATUS), ("err", sh.R_ERR), ("seed", sh.R_SEED),
+                        ("last_trade", sh.R_LAST), ("order_counter", sh.R_OCNT), ("cash", sh.R_CASH),
+                        ("holdings", sh.R_HOLD), ("gain", sh.R_GAIN)):
+            out["records_" + name] = g[:, w].astype(np.float64)
+        for name, w in (("hash", sh.R_HASH), ("time", sh.R_TIME)):
+            out["records_%s_hi" % name] = (g[:, w] >> 32).astype(np.float64)
+            out["records_%s_lo" % name] = (g[:, w] & 0xFFFFFFFF).astype(np.float64)
+        r = np.ascontiguousarray(g[:, sh.R_RETURN])
+        out["records_return"] = r.view(np.float64).copy() if self.return_is_float else r.astype(np.float64)
+        return out
+
+
+DUMP_LIMIT = 64 << 20  # bytes, all files of one --dump-outputs together
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every array; past DUMP_LIMIT in all, each array keeps a fixed seeded sample
+    of its rows (the same rows in every run of the same arguments), in their order"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in sorted(arrays.items()):
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if total > DUMP_LIMIT:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(1, int(len(rows) * (DUMP_LIMIT * 0.98 / total)))
+            a = rows[np.sort(np.random.RandomState(0).choice(len(rows), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 class StubEngine(Engine):
@@ -440,6 +494,15 @@ class GymEngine(Engine):
         kms = [a.elapsed_time(b) for a, b in self.ev_pairs]
         self.launches, self.kernel_ms = len(kms), sum(kms)
 
+    def outputs(self):
+        """the records, and this rank's observations and flags of the last launch (the whole
+        episode's, [steps, envs, ...], unless --per-step)"""
+        import numpy as np
+        out = super().outputs()
+        out["obs"] = self.obs.cpu().numpy()
+        out["flags"] = self.flags.cpu().numpy().astype(np.float32)
+        return out
+
     def count(self, k):
         """one more episode of the same workload (batch k's seeds, fresh actions of the same
         distribution) with the instrumentation on: the algorithmic-byte counters"""
@@ -531,6 +594,7 @@ class DDQNEngine(Engine):
     """rmsc03 + DummyRL with the DDQN execution learner in the loop (mxabides.ddqn): actions from
     the shared Q-network (epsilon-greedy), transitions to the device replay ring, a training
     update every 5 periods as the reference agent does.  Learner state persists across steps."""
+    return_is_float = True
 
     def __init__(self, args, ctx):
         super().__init__(args, ctx)
@@ -736,6 +800,10 @@ def main():
         eng.finish_timing()
     chk = eng.check_gathered() if ctx.rank == 0 else None
     n_err = eng.env_errors()
+    if args.dump_outputs and ctx.rank == 0:  # before any --full leg steps the engine again
+        if args.steps < 1:
+            raise SystemExit("--dump-outputs needs at least one timed step")
+        dump_outputs(args.dump_outputs, eng.outputs())
 
     if ctx.rank == 0:
         d = eng.describe()
@@ -755,6 +823,7 @@ def main():
         if not args.stub:
             out["config"]["device"] = torch.cuda.get_device_name(ctx.local)
             out["config"]["cus"] = torch.cuda.get_device_properties(ctx.local).multi_processor_count
+        if args.full and not args.stub:
             avg_ms = eng.kernel_ms / max(1, eng.launches)
             my_ev_per_launch = events / ctx.world / max(1, eng.launches)
             from mxabides import counters as mc

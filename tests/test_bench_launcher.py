@@ -38,6 +38,22 @@ def test_bench_launcher_world2_gathers_in_global_env_order():
     assert out["value"] > 0 and out["scaling"] == "weak"
 
 
+def test_bench_dump_outputs_writes_last_steps_records(tmp_path):
+    """--dump-outputs: the gathered records of the last timed batch (batch 2 of warmup 1 + steps 2),
+    one float64 file per word, 64-bit words as exact halves; --steps sets the timed steps"""
+    out = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--envs", "3", "--dump-outputs", str(tmp_path / "d"))
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    sys.path.insert(0, os.path.join(ROOT, "marl-optimal-execution_amd"))
+    from mxabides import shard
+    seeds = np.concatenate([shard.env_seeds(2, r, 2, 3) for r in range(2)]).astype(np.int64)
+    got = {f[:-4]: np.load(str(tmp_path / "d" / f)) for f in sorted(os.listdir(str(tmp_path / "d")))}
+    assert len(got) == shard.RECORD_WORDS + 2  # hash and time as _hi / _lo
+    assert all(a.dtype == np.float64 and a.shape == (6,) for a in got.values())
+    assert (got["records_seed"] == seeds).all() and (got["records_events"] == 1000 + seeds % 997).all()
+    assert (got["records_hash_hi"] * 2.0 ** 32 + got["records_hash_lo"] == seeds * 31).all()
+    assert (got["records_status"] == 1).all() and not got["records_return"].any()
+
+
 def test_bench_launcher_single_rank():
     out = _bench("--steps", "1", "--warmup", "0", "--envs", "5")
     assert out["n_gpus"] == 1 and out["config"]["global_envs"] == 5

@@ -15,7 +15,8 @@ from mxabides import tape
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 TAPE = os.path.join(GOLD, "tape_IBM_2003-01-14.npz")
-LOB = "/root/reference/data/lobster/LOBSTER_SampleFile_%s_1/%s_%s_34200000_57600000_message_1.csv"
+# the LOBSTER sample message files themselves (gzip of the CSV, which pandas reads as it is)
+LOB = os.path.join(GOLD, "lobster", "%s_%s_34200000_57600000_message_1.csv.gz")
 EPISODES = [("IBM", "2003-01-14"), ("GOOG", "2012-06-21"), ("IBM", "2003-01-13"), ("YHOO", "2003-01-14")]
 OBS_RTOL = 1e-9  # observations are float64 (numpy log/tanh/std vs glibc): north_star tolerance
 
@@ -41,9 +42,7 @@ def test_tape_fixture_well_formed():
 
 @pytest.mark.parametrize("ticker,date", EPISODES)
 def test_tape_loader_matches_committed_tape(ticker, date):
-    csv = LOB % (ticker, ticker, date)
-    if not os.path.exists(csv):
-        pytest.skip("reference data not present (GPU box)")
+    csv = LOB % (ticker, date)
     a, b = tape.load_lobster(csv, date), tape.Tape.load(_tape(ticker, date))
     for k in ("t", "oid", "price", "size", "buy"):
         assert (getattr(a, k) == getattr(b, k)).all(), k

@@ -13,7 +13,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do CFGS+=("$1"); shift; done
 for c in "${CFGS[@]}"; do
   IFS=: read cfg envs <<< "$c"
   E=${envs:+--envs $envs}
-  timeout -k 10 400 python bench.py --config $cfg $E "$@" > $O/bench_${cfg}_${envs:-default}.json 2> $O/bench_${cfg}.err \
+  timeout -k 10 400 python bench.py --full --config $cfg $E "$@" > $O/bench_${cfg}_${envs:-default}.json 2> $O/bench_${cfg}.err \
     || { echo "bench $cfg failed"; tail $O/bench_${cfg}.err; exit 1; }
   python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], '%.4g' % d['value'], 'ms/step %.1f' % d['ms_per_step'], 'kernel %.2f ms' % d.get('roofline',{}).get('avg_launch_ms',0), 'err', d['config']['env_errors'], 'cpu %.4g' % d.get('cpu_baseline',{}).get('value',0))" $O/bench_${cfg}_${envs:-default}.json $cfg
 done

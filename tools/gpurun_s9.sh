@@ -7,7 +7,7 @@ timeout -k 10 1000 python -u -m pytest tests -x -v --timeout 600 --timeout-metho
 tail -1 $O/pytest_gpu.log
 for spec in "marketreplay:IBM_2003-01-14" "marketreplay:GOOG_2012-06-21" "rmsc03_rl:"; do
   IFS=: read cfg tp <<< "$spec"
-  a="--config $cfg --no-cpu --no-latency --steps 3"; [ -n "$tp" ] && a="$a --tape $tp"
+  a="--full --config $cfg --no-cpu --no-latency --steps 3"; [ -n "$tp" ] && a="$a --tape $tp"
   for v in many per; do
     x=""; [ $v = per ] && x="--per-step"
     timeout -k 10 400 python bench.py $a $x > $O/bench_${cfg}_${tp}_$v.json 2> $O/bench_${cfg}_${tp}_$v.err || { tail $O/bench_${cfg}_${tp}_$v.err; exit 1; }

@@ -12,7 +12,7 @@ if [ -n "$TESTS" ]; then
 fi
 for b in $BENCH; do
   IFS=: read cfg envs tape <<< "$b"
-  args="--config $cfg --no-cpu"
+  args="--full --config $cfg --no-cpu"
   [ -n "$envs" ] && args="$args --envs $envs"
   [ -n "$tape" ] && args="$args --tape $tape"
   name=$cfg${tape:+_$tape}
