@@ -56,6 +56,7 @@ stream does not.
 Everything runs on the device stream the env steps on; the only host read is the stored-transition
 count, when the replay ring's host-side bounds cannot decide the batch-size test.
 """
+import ctypes
 import math
 import os
 
@@ -196,13 +197,30 @@ class DDQNLearner:
     elementwise passes and every update can be masked on the device: `learn(live=...)` with a
     device bool makes the whole update (target copy, RMSprop step and its state, epsilon,
     `learn_step_counter`) a no-op when it is false, without a host read. The counter and epsilon
-    are device scalars for the same reason."""
+    are device scalars for the same reason.
+
+    `fused_act` (include/mxa_qnet.h): every forward without a gradient (q_values, and so
+    choose_action and act; q_target's target(s2) and eval(s)) runs in libmxa_qnet.so's kernel,
+    and choose_action / act make the forward, the argmax and the epsilon-greedy select one launch.
+    The exploration draws are the same two torch calls, so the stream `gen` and every exploring
+    env's action are unchanged; Q-values differ from hipBLASLt's in the last bits (another
+    summation order). True needs a CUDA device, dtype float32 and the library, else RuntimeError;
+    None (the default) turns it on only where the environment has MXA_DDQN_FUSED_ACT=1 and those
+    three hold. train_on_batch's gradient pass stays on autograd."""
 
     def __init__(self, n_state=2, n_actions=N_ACTIONS, replace_target_iter=5, batch_size=32, learning_rate=0.01,
                  epsilon_increment=None, epsilon_max=0.9, reward_decay=0.98, mode="train", model="NNModel_1",
-                 dropout=0.1, capacity=1 << 20, device="cuda", seed=0, dtype=torch.float32, group=None):
+                 dropout=0.1, capacity=1 << 20, device="cuda", seed=0, dtype=torch.float32, group=None,
+                 fused_act=None):
         self.device = torch.device(device)
         self.dtype = dtype
+        can_fuse = self.device.type == "cuda" and dtype == torch.float32 and qnet_lib() is not None
+        if fused_act and not can_fuse:
+            raise RuntimeError("DDQNLearner(fused_act=True) needs a CUDA device, dtype float32 and libmxa_qnet.so "
+                               "(build_lib.build_qnet)")
+        if fused_act is None:
+            fused_act = os.environ.get("MXA_DDQN_FUSED_ACT") == "1" and can_fuse
+        self.fused_act = bool(fused_act)
         self.gen = torch.Generator(device=self.device)  # choose_action's exploration
         self.gen.manual_seed(seed)
         self.gen_sample = torch.Generator(device=self.device)  # train_neural_nets' batch indices
@@ -216,6 +234,9 @@ class DDQNLearner:
         self.eval_model, self.eflat = self._flat(QNet(n_state, n_actions, model, dropout, cpu))
         self.target_model, self.tflat = self._flat(QNet(n_state, n_actions, model, dropout, cpu))
         self.n_actions = n_actions
+        # the layer widths, as mxa_qnet_* take them (a host array)
+        widths = [n_state] + [lin.out_features for lin in self.eval_model.hidden] + [n_actions]
+        self._qdims = (ctypes.c_int * len(widths))(*widths)
         self.replace_target_iter = replace_target_iter
         self.batch_size = batch_size
         self.learning_rate = learning_rate
@@ -287,13 +308,68 @@ class DDQNLearner:
                 for w in self.eval_model.dropout_widths()]
 
     # ---- acting (choose_action, :333-362)
+    def _qnet_forward(self, flat, s):
+        """mxa_qnet_forward of the net whose parameters are `flat` (eflat or tflat)"""
+        x = s.detach().to(torch.float32).contiguous()
+        q = torch.empty((x.shape[0], self.n_actions), dtype=torch.float32, device=self.device)
+        rc = qnet_lib().mxa_qnet_forward(torch.cuda.current_stream().cuda_stream, x.shape[0], x.data_ptr(),
+                                         flat.data_ptr(), len(self._qdims) - 1, self._qdims, q.data_ptr())
+        if rc:
+            raise RuntimeError("mxa_qnet_forward: hip error %d" % rc)
+        return q
+
     def q_values(self, s):
+        if self.fused_act:
+            return self._qnet_forward(self.eflat, s)
         self.eval_model.eval()  # Keras predict(): training=False, no dropout
         with torch.no_grad():
             return self.eval_model(s.to(self.dtype))
 
+    def act(self, s, obs=None, task=None, out_a=None, out_act=None):
+        """fused_act only: choose_action(s) and, with `obs` and `task`, ExecutionTask.actions of
+        it, in one launch (mxa_qnet_act). Fills out_a [n] int64 and out_act [n, 3] float64 (made
+        here when None) and returns them; without obs only the actions are made."""
+        if not self.fused_act:
+            raise RuntimeError("DDQNLearner.act needs fused_act")
+        x = s.detach().to(torch.float32).contiguous()
+        n = x.shape[0]
+        test = self.mode == "test"
+        if out_a is None:
+            out_a = torch.empty(n, dtype=torch.int64, device=self.device)
+        obs_w, obs_p, tab_p, act_p, q0 = 2, None, None, None, 1.0
+        if obs is not None:
+            if out_act is None:
+                out_act = torch.empty((n, 3), dtype=torch.float64, device=self.device)
+            table = task.table
+            if obs.dtype != torch.float64 or obs.dim() != 2 or obs.shape[0] != n or obs.shape[1] < 2 \
+                    or not obs.is_contiguous():
+                raise ValueError("act: obs must be a contiguous float64 [n, w >= 2] tensor")
+            if table.dtype != torch.float64 or table.dim() != 2 or table.shape[0] < self.n_actions \
+                    or table.shape[1] != 3 or not table.is_contiguous():
+                raise ValueError("act: task.table must be a contiguous float64 [>= n_actions, 3] tensor")
+            if out_act.dtype != torch.float64 or tuple(out_act.shape) != (n, 3) or not out_act.is_contiguous():
+                raise ValueError("act: out_act must be a contiguous float64 [n, 3] tensor")
+            obs_w, obs_p, tab_p, act_p, q0 = obs.shape[1], obs.data_ptr(), table.data_ptr(), out_act.data_ptr(), task.q0
+        if out_a.dtype != torch.int64 or tuple(out_a.shape) != (n,) or not out_a.is_contiguous():
+            raise ValueError("act: out_a must be a contiguous int64 [n] tensor")
+        u = rnd = None
+        enough = False
+        if not test:  # the same draws, in the same order, as the unfused choose_action
+            u = torch.rand(n, generator=self.gen, device=self.device, dtype=torch.float64)
+            rnd = torch.randint(0, self.n_actions, (n,), generator=self.gen, device=self.device)
+            enough = self.memory.more_than(self.batch_size - 1)  # len + 1 > batch_size
+        rc = qnet_lib().mxa_qnet_act(torch.cuda.current_stream().cuda_stream, n, x.data_ptr(), self.eflat.data_ptr(),
+                                     len(self._qdims) - 1, self._qdims, int(test), int(enough),
+                                     None if test else u.data_ptr(), None if test else rnd.data_ptr(),
+                                     self._eps.data_ptr(), obs_w, obs_p, tab_p, q0, out_a.data_ptr(), act_p, None)
+        if rc:
+            raise RuntimeError("mxa_qnet_act: hip error %d" % rc)
+        return out_a, out_act
+
     def choose_action(self, s):
         """s [n, n_state] -> actions [n] int64 (epsilon-greedy per env in train mode)."""
+        if self.fused_act:
+            return self.act(s)[0]
         n = s.shape[0]
         greedy = torch.argmax(self.q_values(s), dim=1)
         if self.mode == "test":
@@ -306,6 +382,13 @@ class DDQNLearner:
     # ---- learning (train_neural_nets, :448-515)
     def q_target(self, s, a, s2, r):
         """the reference's target: both q_next and q_eval4next from the target net (:486-505)."""
+        if self.fused_act:  # the two forwards of the target net are one and the same: computed once
+            q_next = self._qnet_forward(self.tflat, s2)
+            tgt = self._qnet_forward(self.eflat, s)
+            idx = torch.arange(s.shape[0], device=self.device)
+            best = torch.argmax(q_next, dim=1)
+            tgt[idx, a] = r.to(self.dtype) + self.reward_decay * q_next[idx, best]
+            return tgt
         self.target_model.eval()
         self.eval_model.eval()
         with torch.no_grad():
@@ -453,6 +536,25 @@ def period_lib():
     return _PERIOD_LIB
 
 
+_QNET_LIB = None
+
+
+def qnet_lib():
+    """libmxa_qnet.so (include/mxa_qnet.h): the Q-network forward and epsilon-greedy action kernel
+    of DDQNLearner(fused_act=True); None when it is not built"""
+    global _QNET_LIB
+    if _QNET_LIB is None:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "libmxa_qnet.so")
+        if not os.path.exists(path):
+            return None
+        L = ctypes.CDLL(path)
+        P, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+        L.mxa_qnet_forward.argtypes = [P, I, P, P, I, ctypes.POINTER(I), P]
+        L.mxa_qnet_act.argtypes = [P, I, P, P, I, ctypes.POINTER(I), I, I, P, P, P, I, P, P, D, P, P, P]
+        _QNET_LIB = L
+    return _QNET_LIB
+
+
 def _state_device(L, task, obs, out):
     rc = L.mxa_ddqn_state(torch.cuda.current_stream().cuda_stream, obs.shape[0], obs.shape[1], obs.data_ptr(),
                           task.grid[0].data_ptr(), task.grid[0].numel(), task.grid[1].data_ptr(), task.grid[1].numel(),
@@ -509,11 +611,14 @@ def _run_episode_fused(L, env, learner, task, seeds, train_every, updates_per_tr
     table = task.table.contiguous()
     act = torch.empty((n, 3), dtype=torch.float64, device=dev)
     for step_counter in range(nh):
-        a = learner.choose_action(s).contiguous()
-        rc = L.mxa_ddqn_actions(torch.cuda.current_stream().cuda_stream, n, obs.shape[1], obs.data_ptr(), a.data_ptr(),
-                                table.data_ptr(), task.q0, act.data_ptr())
-        if rc:
-            raise RuntimeError("mxa_ddqn_actions: hip error %d" % rc)
+        if learner.fused_act:  # forward, epsilon-greedy select and action vector in one launch
+            a, _ = learner.act(s, obs, task, out_act=act)
+        else:
+            a = learner.choose_action(s).contiguous()
+            rc = L.mxa_ddqn_actions(torch.cuda.current_stream().cuda_stream, n, obs.shape[1], obs.data_ptr(),
+                                    a.data_ptr(), table.data_ptr(), task.q0, act.data_ptr())
+            if rc:
+                raise RuntimeError("mxa_ddqn_actions: hip error %d" % rc)
         if record is not None:
             record.append(act.clone())
         st, prev = prev, st  # write_rl_state fills the other buffer: prev keeps the state before the step
