@@ -8,7 +8,8 @@
 // each a few microseconds on a 4096-env batch; here it is one workgroup of 1024 lanes walking the
 // envs in blocks of 1024 with one block-wide prefix count for the replay positions.  Every float
 // operation is the PyTorch path's, in the same order (built with -ffp-contract=off), so the outputs
-// are bitwise the same (tests/test_gpu_ddqn.py compares the two paths).
+// are bitwise the same (tests/test_gpu_ddqn.py compares the two paths), and both equal the plain
+// float64 references of oracle/ddqn_ref.py exactly (tests/test_gpu_ddqn_kernels.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -26,15 +27,19 @@ __device__ int64_t upper_bound(double x, const double* bd, int n) {
   return lo;
 }
 
-// PyTorch divides a tensor by a Python scalar as a multiplication by the scalar's reciprocal
-// (the true-division kernel's CPU-scalar case), which rounds differently from x / b
+// PyTorch on the device divides a tensor by a Python scalar as a multiplication by the scalar's
+// reciprocal (the true-division kernel's CPU-scalar case), which rounds differently from x / b.
+// Only the action's quantity share is computed so (ExecutionTask.actions: the engine places
+// rint(q0 * x) shares, the same integer either way); the state divides truly, see state_of
 __device__ double div_scalar(double x, double b) { return x * (1.0 / b); }
 
-// ExecutionTask.state: discretize([2 * rem_t / nh - 1, 2 * rem_q / q0 - 1])
+// ExecutionTask.state: discretize([2 * rem_t / nh - 1, 2 * rem_q / q0 - 1]) with true divisions,
+// as the reference's numpy (ddqlearning_execution_agent.py:307-308): the reciprocal form lands
+// one bin higher at 73 of the quantities 0..100000 (multiples of 250 from 50250 up)
 __device__ void state_of(const double* o, const double* g0, int n0, const double* g1, int n1, double nh, double q0,
                          float* out) {
-  const double tr = 2.0 * div_scalar(o[0], nh) - 1.0;
-  const double qr = 2.0 * div_scalar(o[1], q0) - 1.0;
+  const double tr = 2.0 * (o[0] / nh) - 1.0;
+  const double qr = 2.0 * (o[1] / q0) - 1.0;
   out[0] = (float)upper_bound(tr, g0, n0);
   out[1] = (float)upper_bound(qr, g1, n1);
 }
@@ -156,14 +161,15 @@ int mxa_ddqn_actions(hipStream_t stream, int n, int obs_w, const double* obs, co
   return (int)hipGetLastError();
 }
 
-// one period's bookkeeping (see PeriodArgs); 0 on success, else the hipError_t of the launch
+// one period's bookkeeping (see PeriodArgs); 0 on success, else the hipError_t of the launch.
+// train with n > cap could put two rows on one ring position, the winner unspecified: refused
 int mxa_ddqn_period(hipStream_t stream, int n, int obs_w, int st_w, int train, const double* obs, const double* st,
                     const double* prev, const double* arrival, const int32_t* flags, const uint8_t* alive,
                     uint8_t* alive_next, uint8_t* live, const float* s, const int64_t* a, float* s2, double* r_row,
                     int64_t* env_steps, const double* g0, int n0, const double* g1, int n1, double nh, double q0,
                     double rscale, float* ring_s, float* ring_s2, int64_t* ring_a, float* ring_r, int64_t cap,
                     int64_t* n_dev, int64_t* stored) {
-  if (n < 0 || cap <= 0 || obs_w < 2 || st_w < 3) return (int)hipErrorInvalidValue;
+  if (n < 0 || cap <= 0 || obs_w < 2 || st_w < 3 || (train && n > cap)) return (int)hipErrorInvalidValue;
   PeriodArgs p{n, obs_w, st_w, train, obs, st, prev, arrival, flags, alive, alive_next, live, s, a, s2, r_row,
                env_steps, g0, g1, n0, n1, nh, q0, rscale, ring_s, ring_s2, ring_r, ring_a, cap, n_dev, stored};
   hipLaunchKernelGGL(ddqn_period_kernel, dim3(1), dim3(1024), 0, stream, p);

@@ -7,7 +7,10 @@ parallel envs on one device:
 * the 24-action table: SIZE_ALLOCATION x SIZE_SCALE (ddqlearning_execution_agent.py:21-37);
 * the state: `discretize([time_remaining, qty_remaining, ...], grid)` on a 200 x 200 uniform grid
   over [0, 1]^2 (:129, :301-331; agent/execution/util.py:5-40). `discretize` zips the six
-  features with the two grid axes, so the state is the two bin indices of time and quantity;
+  features with the two grid axes, so the state is the two bin indices of time and quantity.
+  Both features divide truly (remaining / total), on the CPU, in the PyTorch ops on the device
+  and in libmxa_ddqn.so's kernels alike, so all three give np.digitize's bins of the reference's
+  own expressions (oracle/ddqn_ref.state_ref; a multiply by 1/quantity would not);
 * the Q-network NNModel_1 (util/model/QNets.py:7-27: Dense 32-64-128-128-64-32 ReLU, Dropout 0.1
   after layers 2-6, linear 24-way head; Keras defaults glorot_uniform / zero bias), EvalModel and
   TargetModel (QNets.py:54-60); NNModel_2 (:30-51) by name;
@@ -488,11 +491,17 @@ class ExecutionTask:
         for k, (alloc, scale) in ACTIONS.items():
             tab[k] = (max(0, round(scale * self.child)) / self.q0,) + LEVEL_SHARES[alloc]
         self.table = torch.tensor(tab, dtype=torch.float64, device=device)
+        # the state's divisors as 0-dim device tensors: a tensor / tensor division is a true
+        # division on every device, where tensor / Python scalar on a CUDA device multiplies by
+        # the scalar's reciprocal and lands one bin off np.digitize at 73 of the quantities 0..1e5
+        self._nh = torch.tensor(float(self.nh), dtype=torch.float64, device=device)
+        self._q0 = torch.tensor(self.q0, dtype=torch.float64, device=device)
 
     def state(self, obs):
-        """discretize([2*rem_t/len - 1, 2*rem_q/q0 - 1]) -> float [n, 2] bin indices."""
-        tr = 2 * (obs[:, 0] / self.nh) - 1
-        qr = 2 * (obs[:, 1] / self.q0) - 1
+        """discretize([2*rem_t/len - 1, 2*rem_q/q0 - 1]) -> float [n, 2] bin indices; true
+        divisions, as the reference's numpy (:307-308; oracle/ddqn_ref.state_ref)."""
+        tr = 2 * (obs[:, 0] / self._nh) - 1
+        qr = 2 * (obs[:, 1] / self._q0) - 1
         # np.digitize(x, increasing bins) == torch.bucketize(x, bins, right=True)
         return torch.stack([torch.bucketize(tr, self.grid[0], right=True),
                             torch.bucketize(qr, self.grid[1], right=True)], 1).to(torch.float32)
@@ -501,6 +510,8 @@ class ExecutionTask:
         """DDQN action index -> DummyRL action vector [n, 3] float64 (take_action, :364-407)."""
         act = self.table[a].clone()
         last = obs[:, 0] == 1  # remaining_time == 1: the whole remaining quantity, allocation 0
+        # x = qty / q0 by a Python scalar (on a CUDA device: qty * (1 / q0)); the engine places
+        # rint(q0 * x) shares, the quantity itself either way (oracle/ddqn_ref.rint_of_share_is_exact)
         act[:, 0] = torch.where(last, obs[:, 1] / self.q0, act[:, 0])
         act[:, 1] = torch.where(last, torch.ones_like(act[:, 1]), act[:, 1])
         act[:, 2] = torch.where(last, torch.zeros_like(act[:, 2]), act[:, 2])
@@ -568,7 +579,9 @@ def run_episode(env, learner, task, seeds=None, train_every=5, updates_per_train
                 fused=None):
     """fused (default: a learner on the GPU with libmxa_ddqn.so built): the bookkeeping after each
     step in one kernel (include/mxa_ddqn.h), bitwise the same as the PyTorch ops that fused=False
-    runs (tests/test_gpu_ddqn.py; 59.9 -> 55.8 ms per rmsc03_ddqn x4096 episode on one box)."""
+    runs (tests/test_gpu_ddqn.py; 59.9 -> 55.8 ms per rmsc03_ddqn x4096 episode on one box); both
+    equal the plain float64 references of oracle/ddqn_ref.py (tests/test_gpu_ddqn_kernels.py).
+    The kernel refuses a training batch of more envs than the replay capacity."""
     L = period_lib() if fused is not False and learner.device.type == "cuda" else None
     if fused and L is None:
         raise RuntimeError("run_episode(fused=True): libmxa_ddqn.so is not built (build_lib.build_ddqn)")

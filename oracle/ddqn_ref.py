@@ -104,3 +104,128 @@ def train_step(eval_layers, target_layers, rms, counter, batch, lr=0.01, gamma=0
     loss, grads = mse_grads(eval_layers, s, tgt, masks, rate)
     eval_layers, rms = rmsprop_step(eval_layers, grads, rms, lr)
     return eval_layers, target_layers, rms, counter + 1, loss
+
+
+# ---- plain references of the device kernels (include/mxa_ddqn.h, include/mxa_qnet.h).  float64
+# IEEE arithmetic, one rounding per operation, nothing taken from the code under test: the kernels'
+# tests compare with exact equality.
+
+def state_ref(obs, g0, g1, nh, q0):
+    """ddqlearning_execution_agent.py:301-331 with agent/execution/util.py:25-40: the bin indices
+    [n, 2] (int64) of 2 * remaining_time / len - 1 and 2 * remaining_qty / quantity - 1, true
+    divisions, np.digitize (NaN and +inf -> len(bins), -inf -> 0)."""
+    obs = np.asarray(obs, dtype=np.float64)
+    out = np.zeros((len(obs), 2), dtype=np.int64)
+    if len(obs):
+        out[:, 0] = np.digitize(2 * (obs[:, 0] / float(nh)) - 1, np.asarray(g0, dtype=np.float64))
+        out[:, 1] = np.digitize(2 * (obs[:, 1] / float(q0)) - 1, np.asarray(g1, dtype=np.float64))
+    return out
+
+
+def actions_ref(obs, a, table, q0):
+    """take_action (:364-407) as the DummyRL action vector [n, 3]: the table's row of a, or on the
+    last horizon step (obs[0] == 1) the whole remaining quantity at allocation (1, 0).  The
+    quantity share is obs[1] * (1 / q0), the device's arithmetic: the engine places
+    rint(q0 * x) shares, which is the quantity itself either way (rint_of_share_is_exact)."""
+    out = np.zeros((len(a), 3), dtype=np.float64)
+    inv = 1.0 / float(q0)
+    for i in range(len(a)):
+        if obs[i][0] == 1.0:
+            out[i] = (obs[i][1] * inv, 1.0, 0.0)
+        else:
+            out[i] = table[int(a[i])]
+    return out
+
+
+def rint_of_share_is_exact(q0, q_max):
+    """rint(q0 * (q * (1 / q0))) == q for every integer quantity 0..q_max"""
+    q = np.arange(int(q_max) + 1, dtype=np.float64)
+    return bool(np.all(np.rint(float(q0) * (q * (1.0 / float(q0)))) == q))
+
+
+def period_ref(n, obs_w, st_w, train, obs, st, prev, arrival, flags, alive, s, a, env_steps, g0, n0, g1, n1, nh, q0,
+               rscale, ring_s, ring_s2, ring_a, ring_r, cap, n_dev, stored):
+    """One period of the learner loop (place_order, :275-299) for n envs, the arguments of
+    mxa_ddqn_period as numpy arrays; the inputs are left unchanged and every output is returned.
+    ok = alive & obs valid (flag bit 1) & no env error (bit 2); the reward is compute_reward summed
+    over the step's fills (BUY): rscale * (2 dq + dcash / arrival) when dq > 0, else 0; the ok
+    envs' rows (s, a, s2, float32(r)) are appended in env order at (n_dev + k) % cap."""
+    obs = np.asarray(obs, dtype=np.float64).reshape(n, obs_w)
+    st = np.asarray(st, dtype=np.float64).reshape(n, st_w)
+    prev = np.asarray(prev, dtype=np.float64).reshape(n, st_w)
+    s2 = state_ref(obs, g0[:n0], g1[:n1], nh, q0).astype(np.float32)
+    alive_next = np.zeros(n, dtype=bool)
+    r_row = np.zeros(n, dtype=np.float64)
+    env_steps = np.array(env_steps, dtype=np.int64)
+    ring_s, ring_s2 = np.array(ring_s, dtype=np.float32), np.array(ring_s2, dtype=np.float32)
+    ring_a, ring_r = np.array(ring_a, dtype=np.int64), np.array(ring_r, dtype=np.float32)
+    n_dev, stored = int(n_dev), int(stored)
+    live = False
+    k = 0
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            f = int(flags[i])
+            al = bool(alive[i])
+            live = live or al
+            ok = al and (f & 2) != 0 and (f & 4) == 0
+            dq = st[i, 2] - prev[i, 2]
+            dcash = st[i, 0] - prev[i, 0]
+            r = np.float64(rscale) * (2.0 * dq + dcash / np.float64(arrival[i])) if dq > 0 else np.float64(0.0)
+            env_steps[i] += 1 if al else 0
+            r_row[i] = r if ok else 0.0
+            alive_next[i] = ok and (f & 1) == 0
+            if train and ok:
+                pos = (n_dev + k) % int(cap)
+                ring_s[pos] = s[i]
+                ring_s2[pos] = s2[i]
+                ring_a[pos] = a[i]
+                ring_r[pos] = np.float32(r)
+                k += 1
+    return {"alive_next": alive_next, "live": live, "s2": s2, "r_row": r_row, "env_steps": env_steps,
+            "ring_s": ring_s, "ring_s2": ring_s2, "ring_a": ring_a, "ring_r": ring_r,
+            "n_dev": n_dev + k, "stored": stored + k}
+
+
+def qnet_ref(layers, x):
+    """Keras predict of a Dense stack (QNets.py:7-51) in float64: layers [(W [in, out], b)], ReLU
+    on all but the last; a NaN passes through the ReLU."""
+    h = np.asarray(x, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for i, (W, b) in enumerate(layers):
+            h = h @ np.asarray(W, dtype=np.float64) + np.asarray(b, dtype=np.float64)
+            if i + 1 < len(layers):
+                h = np.where(h < 0, 0.0, h)
+    return h
+
+
+def integer_net(dims, n_rows, seed, nnz=None):
+    """A net and n_rows inputs whose float32 fmaf chain is exact in any summation order: inputs
+    integers in [-4, 4], biases integers in [-3, 3], weights from {-2, -1, 1, 2} (with `nnz`, that
+    many nonzeros per neuron at random inputs, else dense).  Asserts that sum_k |a_k| |w_k| + |b|
+    < 2**24 for every neuron and every row (a condition on the inputs: every partial sum is then
+    an integer that float32 holds), so the float32 result must equal qnet_ref bit for bit.
+    Returns (layers [(W [in, out], b)], x [n_rows, dims[0]], the worst such sum)."""
+    rs = np.random.RandomState(seed)
+    x = rs.randint(-4, 5, (n_rows, dims[0])).astype(np.float64)
+    layers, h, worst = [], x, 0.0
+    for i in range(len(dims) - 1):
+        n_in, n_out = dims[i], dims[i + 1]
+        W = rs.choice([-2.0, -1.0, 1.0, 2.0], (n_in, n_out))
+        if nnz is not None and nnz < n_in:
+            keep = np.zeros((n_in, n_out), dtype=bool)
+            for j in range(n_out):
+                keep[rs.choice(n_in, nnz, replace=False), j] = True
+            W = W * keep
+        b = rs.randint(-3, 4, n_out).astype(np.float64)
+        bound = np.abs(h) @ np.abs(W) + np.abs(b)
+        worst = max(worst, float(bound.max()))
+        assert bound.max() < 2 ** 24, (dims, i, float(bound.max()))
+        layers.append((W, b))
+        h = np.maximum(h @ W + b, 0.0)  # the next layer's inputs
+    return layers, x, worst
+
+
+def flat_params(layers):
+    """the flat float32 parameter buffer of include/mxa_qnet.h: per layer weight[out][in]
+    row-major, then bias[out]"""
+    return np.concatenate([np.concatenate([W.T.reshape(-1), b]) for W, b in layers]).astype(np.float32)

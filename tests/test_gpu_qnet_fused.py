@@ -1,6 +1,8 @@
 """include/mxa_qnet.h on the GPU: the hand-written Q-network forward and epsilon-greedy action
 kernel (libmxa_qnet.so, DDQNLearner(fused_act=True)) against an fp64 forward of the same weights,
-over the whole 200 x 200 state space, and the learner paths built on it."""
+over the whole 200 x 200 state space, and the learner paths built on it; then the kernel's edges
+(odd widths, both staging paths, all of its LDS, every output of mxa_qnet_act, the select's and
+the argmax's branches) with exact equality against oracle/ddqn_ref.py."""
 import copy
 import ctypes
 
@@ -8,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import ddqn_kernel_util as U
+import ddqn_ref
 from mxabides import ddqn
 
 pytestmark = pytest.mark.gpu
@@ -273,3 +277,147 @@ def test_gpu_qnet_fused_episode_matches_oracle_replay():
     assert learner.learn_step_counter > 0
     cost = learner.cost_hist
     assert cost and all(np.isfinite(float(c)) for c in cost)
+
+
+# ---- the kernel's edges, through ctypes, against oracle/ddqn_ref.py's plain float64 forward with
+# exact equality: nets whose fp32 fmaf chain is exact (ddqn_ref.integer_net), so any slip in the
+# staging (16-byte and plain), the pass and tile bounds or the LDS strides shows as wrong bits
+
+def _cdims(dims):
+    return (ctypes.c_int * len(dims))(*dims)
+
+
+def _fwd(flat, dims, x, what):
+    """mxa_qnet_forward on x (numpy), q behind sentinels"""
+    xg = U.Guarded(x.astype(np.float32))
+    q = U.Guarded(np.full((len(x), dims[-1]), -3.0, dtype=np.float32))
+    rc = ddqn.qnet_lib().mxa_qnet_forward(torch.cuda.current_stream().cuda_stream, len(x), xg.ptr, flat.data_ptr(),
+                                          len(dims) - 1, _cdims(dims), q.ptr)
+    assert rc == 0, (what, rc)
+    torch.cuda.synchronize()
+    return q.read(what)
+
+
+def _act(flat, dims, x, test, enough, u, rnd, eps, obs, table, q0, what):
+    """mxa_qnet_act with q, a (and, with obs, act) all requested, each behind sentinels"""
+    n = len(x)
+    xg = U.Guarded(x.astype(np.float32))
+    ug = None if u is None else U.Guarded(np.asarray(u, dtype=np.float64))
+    rg = None if rnd is None else U.Guarded(np.asarray(rnd, dtype=np.int64))
+    eg = U.Guarded(np.array([eps], dtype=np.float64))
+    og = None if obs is None else U.Guarded(obs)
+    tg = None if obs is None else U.Guarded(table)
+    q = U.Guarded(np.full((n, dims[-1]), -3.0, dtype=np.float32))
+    a = U.Guarded(np.full(n, -3, dtype=np.int64))
+    act = None if obs is None else U.Guarded(np.full((n, 3), -3.0))
+    ptr = lambda g: None if g is None else g.ptr
+    rc = ddqn.qnet_lib().mxa_qnet_act(torch.cuda.current_stream().cuda_stream, n, xg.ptr, flat.data_ptr(), len(dims) - 1,
+                                      _cdims(dims), int(test), int(enough), ptr(ug), ptr(rg), eg.ptr,
+                                      2 if obs is None else obs.shape[1], ptr(og), ptr(tg), q0, a.ptr, ptr(act), q.ptr)
+    assert rc == 0, (what, rc)
+    torch.cuda.synchronize()
+    return a.read((what, "a")), None if act is None else act.read((what, "act")), q.read((what, "q"))
+
+
+def _integer_net(dims, nnz, seed):
+    key = ("int", dims)
+    if key not in _CACHE:
+        layers, x, _ = ddqn_ref.integer_net(dims, 100, seed, nnz)
+        flat = torch.from_numpy(ddqn_ref.flat_params(layers)).cuda()
+        shifted = torch.cat([torch.zeros(1, device="cuda"), flat])[1:]
+        assert flat.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 != 0
+        _CACHE[key] = (x, ddqn_ref.qnet_ref(layers, x).astype(np.float32), flat, shifted)
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("dims,nnz,seed", U.INTEGER_NETS)
+def test_gpu_qnet_integer_nets_bit_for_bit(dims, nnz, seed):
+    """widths that are no multiple of 4 (255, 65, 129, 63, 1) or of the 64-neuron pass, the weight
+    strides of in = 4 and in = 12, a three-trip plain staging loop (in = 129, 255), 8 layers of 256
+    (all of the 100,864 B of LDS); one env, a tile less one, a tile, a tile and one, two tiles and
+    one, six tiles and four. The same bits from the parameters one float further on (no 16-byte
+    alignment: the plain staging path for every layer)"""
+    x, ref, flat, shifted = _integer_net(dims, nnz, seed)
+    for n in (1, 15, 16, 17, 33, 100):
+        for name, p in (("aligned", flat), ("shifted", shifted)):
+            q = _fwd(p, dims, x[:n], (dims, n, name))
+            assert U.same(q, ref[:n]), (dims, n, name, int((q != ref[:n]).sum()))
+
+
+@pytest.mark.parametrize("dims,nnz,seed", U.INTEGER_NETS)
+def test_gpu_qnet_act_q_a_and_act_behind_sentinels(dims, nnz, seed):
+    """mxa_qnet_act with all three outputs: q has mxa_qnet_forward's (and so the reference's)
+    bits, a is np.argmax of it where the env exploits and rnd elsewhere, act is actions_ref of a
+    (rows of 2, 9 and 13 doubles, a fifth of them on the last step)"""
+    x, ref, flat, _ = _integer_net(dims, nnz, seed)
+    n_out = dims[-1]
+    rs = np.random.RandomState(n_out)
+    table = rs.rand(n_out, 3)
+    for n, obs_w in ((1, 2), (17, 9), (100, 13), (33, 2)):
+        u = rs.rand(n)
+        rnd = rs.randint(0, n_out, n)
+        obs = rs.rand(n, obs_w) * 100
+        obs[:, 0] = np.resize([1.0, np.nextafter(1.0, 2.0), np.nextafter(1.0, 0.0), np.nan, 2.0], n)
+        obs[:, 1] = rs.randint(0, 100001, n)
+        a, act, q = _act(flat, dims, x[:n], 0, 1, u, rnd, 0.5, obs, table, 1e5, (dims, n))
+        assert U.same(q, ref[:n]) and U.same(q, _fwd(flat, dims, x[:n], (dims, n)))
+        want = np.where(u < 0.5, np.argmax(ref[:n], axis=1), rnd)
+        assert U.same(a, want.astype(np.int64)), (dims, n)
+        assert U.same(act, ddqn_ref.actions_ref(obs, want, table, 1e5)), (dims, n)
+        a2, none, q2 = _act(flat, dims, x[:n], 0, 1, u, rnd, 0.5, None, None, 1.0, (dims, n, "no act"))
+        assert none is None and U.same(a2, a) and U.same(q2, q)
+
+
+def test_gpu_qnet_epsilon_greedy_select_edges():
+    """exploit exactly where u < eps and enough: u just below, at and just above eps = 0.5, 0
+    and the largest double below 1; test mode with null u and rnd is all greedy"""
+    dims, nnz, seed = U.INTEGER_NETS[0]
+    x, ref, flat, _ = _integer_net(dims, nnz, seed)
+    n = 40
+    greedy = np.argmax(ref[:n], axis=1)
+    rnd = (greedy + 1 + np.arange(n) % 22) % 24  # never the greedy action
+    u = np.resize([np.nextafter(0.5, 0.0), 0.5, np.nextafter(0.5, 1.0), 0.0, 1 - 2.0 ** -53], n)
+    assert u[4] < 1.0 and (rnd != greedy).all()
+    for enough in (0, 1):
+        a, _, q = _act(flat, dims, x[:n], 0, enough, u, rnd, 0.5, None, None, 1.0, ("select", enough))
+        exploit = (u < 0.5) & bool(enough)
+        assert exploit.sum() == (16 if enough else 0)
+        assert U.same(a, np.where(exploit, greedy, rnd).astype(np.int64)), enough
+        assert U.same(q, ref[:n])
+    for enough in (0, 1):
+        a, _, _ = _act(flat, dims, x[:n], 1, enough, None, None, 0.5, None, None, 1.0, ("test mode", enough))
+        assert U.same(a, greedy.astype(np.int64))
+
+
+@pytest.mark.parametrize("dims", [(2, 6), (2, 4, 6)])
+def test_gpu_qnet_crafted_maxima(dims):
+    """the argmax's branches: an exact tie (the lower index wins), NaN (the first NaN wins, as
+    np.argmax and torch.argmax), +inf, all -inf, and a NaN input row (action 0; the NaN passes
+    through the ReLU). The expected action is np.argmax of the float64 reference"""
+    rs = np.random.RandomState(len(dims))
+    x = rs.randint(-4, 5, (20, 2)).astype(np.float64)
+    hidden = [(rs.choice([-2.0, -1.0, 1.0, 2.0], (dims[i], dims[i + 1])), np.full(dims[i + 1], 10.0))
+              for i in range(len(dims) - 2)]
+    W = rs.choice([-2.0, -1.0, 1.0, 2.0], (dims[-2], 6))
+    W[:, 3] = W[:, 1]
+    b = np.array([-5000.0, 7.0, -4000.0, 7.0, -3000.0, -2000.0])
+    nan_x = x.copy()
+    nan_x[3] = [np.nan, 1.0]
+    cases = {"tie": (b, x, 1), "nan": (np.array([0.0, 1.0, np.nan, 2.0, np.nan, 3.0]), x, 2),
+             "inf": (np.array([0.0, np.inf, 1.0, 2.0, 3.0, 4.0]), x, 1), "all -inf": (np.full(6, -np.inf), x, 0),
+             "nan row": (b, nan_x, None)}
+    for name, (bias, xs, pick) in cases.items():
+        layers = hidden + [(W, bias)]
+        ref = ddqn_ref.qnet_ref(layers, xs)
+        want = np.argmax(ref, axis=1)
+        if name == "tie":
+            assert np.all(ref[:, 1] == ref[:, 3]) and np.all(ref[:, 1] == ref.max(1))
+        if name == "nan row":
+            assert np.isnan(ref[3]).all() and want[3] == 0 and not np.isnan(np.delete(ref, 3, 0)).any()
+            assert np.all(np.delete(want, 3) == 1)
+        else:
+            assert np.all(want == pick), (name, want)
+        flat = torch.from_numpy(ddqn_ref.flat_params(layers)).cuda()
+        a, _, q = _act(flat, dims, xs, 1, 0, None, None, 0.5, None, None, 1.0, (dims, name))
+        assert np.array_equal(q, ref.astype(np.float32), equal_nan=True), (dims, name)
+        assert np.array_equal(np.isnan(q), np.isnan(ref)) and U.same(a, want.astype(np.int64)), (dims, name, a)
