@@ -1,12 +1,20 @@
-/* mxa_ddqn.h — libmxa_ddqn.so: the DDQN execution learner's per-period bookkeeping on the device
- * (mxabides/ddqn.py run_episode; marl-optimal-execution_amd/csrc/ddqn_period.hip).
+/* mxa_ddqn.h — libmxa_ddqn.so: the DDQN execution learner's kernels on the device (mxabides/ddqn.py;
+ * marl-optimal-execution_amd/csrc/ddqn_period.hip, ddqn_qnet.hip). Pointers are device pointers unless
+ * said otherwise; `stream` is a hipStream_t. Every export returns 0 or a hipError_t.
  *
- * Replaces, per ABIDESEnv.step of a VecABIDESEnv batch, the PyTorch ops that follow the step in
- * the learner loop of agent/execution/ddqlearning_execution_agent.py:275-299 (place_order: the
- * transition, compute_reward :409-446, the next state :301-331, memory.store_transition :115-116)
- * with one launch; bitwise the same results (tests/test_gpu_ddqn.py), and exactly those of the
- * plain float64 references in oracle/ddqn_ref.py (tests/test_gpu_ddqn_kernels.py). Pointers are
- * device pointers; `stream` is a hipStream_t. Returns 0 or a hipError_t. */
+ * The per-period bookkeeping (run_episode; ddqn_period.hip) replaces, per ABIDESEnv.step of a
+ * VecABIDESEnv batch, the PyTorch ops that follow the step in the learner loop of
+ * agent/execution/ddqlearning_execution_agent.py:275-299 (place_order: the transition,
+ * compute_reward :409-446, the next state :301-331, memory.store_transition :115-116) with one
+ * launch; bitwise the same results (tests/test_gpu_ddqn.py), and exactly those of the plain float64
+ * references in oracle/ddqn_ref.py (tests/test_gpu_ddqn_kernels.py).
+ *
+ * The Q-network inference (DDQNLearner(fused_act=True); ddqn_qnet.hip) replaces the PyTorch ops
+ * that precede the step: the Keras predict of NNModel_1 / NNModel_2 (util/model/QNets.py:7-51:
+ * Dense layers, ReLU on all but the last, no dropout), the epsilon-greedy choice (choose_action,
+ * :333-362) and the action vector (take_action, :364-407), with one launch. fp32 with FMA; every
+ * output element is one sum over the layer's inputs in index order, so a row's result is bitwise
+ * the same in any batch. */
 #ifndef MXA_DDQN_H
 #define MXA_DDQN_H
 #include <stdint.h>
@@ -39,6 +47,24 @@ int mxa_ddqn_state(void* stream, int n, int obs_w, const double* obs, const doub
  * horizon step (obs[0] == 1) (obs[1] * (1 / q0), 1, 0); guards as mxa_ddqn_state */
 int mxa_ddqn_actions(void* stream, int n, int obs_w, const double* obs, const int64_t* a, const double* table,
                      double q0, double* act);
+/* mxa_qnet_*: `params` is one flat fp32 buffer holding, for each layer i < n_layers in order,
+ * weight[dims[i+1]][dims[i]] row-major, then bias[dims[i+1]] (DDQNLearner.eflat / tflat). `dims`
+ * is a HOST array of n_layers + 1 widths. Supported: 1 <= n_layers <= 8, every width in 1..256;
+ * anything else, n < 0 or obs_w < 2 returns hipErrorInvalidValue before any HIP call; n == 0
+ * returns 0.
+ * q [n][dims[n_layers]] f32 = MLP(x [n][dims[0]] f32) */
+int mxa_qnet_forward(void* stream, int n, const float* x, const float* params, int n_layers, const int* dims,
+                     float* q);
+/* the same forward, then per row: greedy = the lowest index of the row maximum (a NaN counts as
+ * the maximum, as torch.argmax); a = (!test && !(u < *eps && enough)) ? rnd : greedy, with u [n]
+ * f64, rnd [n] i64 in [0, n_out), eps a device f64 scalar, enough / test host ints (with test set
+ * u, rnd and eps are not read); act [n][3] f64 = table[a] (table [n_out][3] f64), or on the last
+ * horizon step (obs[0] == 1, obs [n][obs_w] f64) (obs[1] * (1 / q0), 1, 0), as mxa_ddqn_actions.
+ * Writes a [n] i64 and act; q [n][n_out] f32 too unless it is null. With act null only a (and q)
+ * are written, and obs and table are not read. a must not be null (n > 0): hipErrorInvalidValue. */
+int mxa_qnet_act(void* stream, int n, const float* x, const float* params, int n_layers, const int* dims, int test,
+                 int enough, const double* u, const int64_t* rnd, const double* eps, int obs_w, const double* obs,
+                 const double* table, double q0, int64_t* a, double* act, float* q);
 #ifdef __cplusplus
 }
 #endif

@@ -91,18 +91,19 @@ def build(force=False, verbose=True, jobs=None):
     return OUT
 
 
-DDQN_SRC = os.path.join(HERE, "csrc", "ddqn_period.hip")
+DDQN_SRCS = [os.path.join(HERE, "csrc", f) for f in ("ddqn_period.hip", "ddqn_qnet.hip")]
+DDQN_DEPS = DDQN_SRCS + [os.path.join(HERE, "csrc", "ddqn_device.h"), os.path.abspath(__file__)]
 DDQN_OUT = os.path.join(HERE, "lib", "libmxa_ddqn.so")
 
 
 def build_ddqn(force=False, verbose=True):
-    """libmxa_ddqn.so: the DDQN learner's per-period bookkeeping kernel (mxabides.ddqn run_episode);
-    a library of its own, outside the engine's build id"""
-    if not force and os.path.exists(DDQN_OUT) and os.path.getmtime(DDQN_OUT) >= max(
-            os.path.getmtime(DDQN_SRC), os.path.getmtime(os.path.abspath(__file__))):
+    """libmxa_ddqn.so (include/mxa_ddqn.h): the DDQN learner's kernels (mxabides.ddqn), the per-period
+    bookkeeping of run_episode and the Q-network forward and epsilon-greedy action of
+    DDQNLearner(fused_act=True); a library of its own, outside the engine's build id"""
+    if not force and os.path.exists(DDQN_OUT) and os.path.getmtime(DDQN_OUT) >= max(map(os.path.getmtime, DDQN_DEPS)):
         return DDQN_OUT
     os.makedirs(os.path.dirname(DDQN_OUT), exist_ok=True)
-    cmd = [HIPCC] + FLAGS + [DDQN_SRC, "-o", DDQN_OUT + ".tmp"]
+    cmd = [HIPCC] + FLAGS + DDQN_SRCS + ["-o", DDQN_OUT + ".tmp"]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
@@ -110,27 +111,6 @@ def build_ddqn(force=False, verbose=True):
     return DDQN_OUT
 
 
-QNET_SRC = os.path.join(HERE, "csrc", "ddqn_qnet.hip")
-QNET_OUT = os.path.join(HERE, "lib", "libmxa_qnet.so")
-
-
-def build_qnet(force=False, verbose=True):
-    """libmxa_qnet.so: the DDQN learner's Q-network forward and epsilon-greedy action kernel
-    (include/mxa_qnet.h; mxabides.ddqn DDQNLearner(fused_act=True)); a library of its own, outside
-    the engine's build id"""
-    if not force and os.path.exists(QNET_OUT) and os.path.getmtime(QNET_OUT) >= max(
-            os.path.getmtime(QNET_SRC), os.path.getmtime(os.path.abspath(__file__))):
-        return QNET_OUT
-    os.makedirs(os.path.dirname(QNET_OUT), exist_ok=True)
-    cmd = [HIPCC] + FLAGS + [QNET_SRC, "-o", QNET_OUT + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    os.replace(QNET_OUT + ".tmp", QNET_OUT)
-    return QNET_OUT
-
-
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_ddqn(force="--force" in sys.argv)
-    build_qnet(force="--force" in sys.argv)

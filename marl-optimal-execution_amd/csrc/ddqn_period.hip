@@ -1,5 +1,5 @@
 // ddqn_period.hip — the DDQN execution learner's per-period bookkeeping in one launch
-// (libmxa_ddqn.so; mxabides/ddqn.py run_episode, fused path).
+// (libmxa_ddqn.so, include/mxa_ddqn.h, with ddqn_qnet.hip; mxabides/ddqn.py run_episode, fused path).
 //
 // After each ABIDESEnv.step of every env the learner loop (ddqlearning_execution_agent.py:275-299,
 // 409-446) needs: the transition mask, the reward of the step's fills (compute_reward, BUY), the
@@ -14,35 +14,9 @@
 
 #include <cstdint>
 
+#include "ddqn_device.h"
+
 namespace {
-
-// torch.bucketize(x, bd, right=True): searchsorted's upper bound, NaN sorting last
-__device__ int64_t upper_bound(double x, const double* bd, int n) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (!(bd[mid] > x)) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// PyTorch on the device divides a tensor by a Python scalar as a multiplication by the scalar's
-// reciprocal (the true-division kernel's CPU-scalar case), which rounds differently from x / b.
-// Only the action's quantity share is computed so (ExecutionTask.actions: the engine places
-// rint(q0 * x) shares, the same integer either way); the state divides truly, see state_of
-__device__ double div_scalar(double x, double b) { return x * (1.0 / b); }
-
-// ExecutionTask.state: discretize([2 * rem_t / nh - 1, 2 * rem_q / q0 - 1]) with true divisions,
-// as the reference's numpy (ddqlearning_execution_agent.py:307-308): the reciprocal form lands
-// one bin higher at 73 of the quantities 0..100000 (multiples of 250 from 50250 up)
-__device__ void state_of(const double* o, const double* g0, int n0, const double* g1, int n1, double nh, double q0,
-                         float* out) {
-  const double tr = 2.0 * (o[0] / nh) - 1.0;
-  const double qr = 2.0 * (o[1] / q0) - 1.0;
-  out[0] = (float)upper_bound(tr, g0, n0);
-  out[1] = (float)upper_bound(qr, g1, n1);
-}
 
 struct PeriodArgs {
   int n, obs_w, st_w, train;
@@ -133,18 +107,12 @@ __global__ __launch_bounds__(256) void ddqn_state_kernel(int n, int obs_w, const
   if (i < n) state_of(obs + (size_t)i * obs_w, g0, n0, g1, n1, nh, q0, s + 2 * i);
 }
 
-// ExecutionTask.actions: the action table's row of a, or on the horizon's last step
-// (remaining time 1) the whole remaining quantity at allocation (1, 0)
+// ExecutionTask.actions (ddqn_device.h action_of) of every env
 __global__ __launch_bounds__(256) void ddqn_actions_kernel(int n, int obs_w, const double* obs, const int64_t* a,
                                                            const double* table, double q0, double* act) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double* t = table + 3 * a[i];
-  const double* o = obs + (size_t)i * obs_w;
-  const bool last = o[0] == 1.0;
-  act[3 * i] = last ? div_scalar(o[1], q0) : t[0];
-  act[3 * i + 1] = last ? 1.0 : t[1];
-  act[3 * i + 2] = last ? 0.0 : t[2];
+  action_of(table + 3 * a[i], obs + (size_t)i * obs_w, q0, act + 3 * i);
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // ddqn_qnet.hip — the DDQN learner's Q-network inference and epsilon-greedy action in one launch
-// (libmxa_qnet.so, include/mxa_qnet.h; mxabides/ddqn.py DDQNLearner(fused_act=True)).
+// (libmxa_ddqn.so, include/mxa_ddqn.h, with ddqn_period.hip; mxabides/ddqn.py DDQNLearner(fused_act=True)).
 //
 // The networks are NNModel_1 / NNModel_2 (util/model/QNets.py:7-51): up to eight Dense layers
 // of at most 256 units, ReLU on all but the last, no dropout (Keras predict).  The work per
@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "ddqn_device.h"
 
 namespace {
 
@@ -178,14 +180,8 @@ __global__ __launch_bounds__(kThreads) void qnet_kernel(QnetArgs p) {
   if (!p.test && !(p.u[i] < *p.eps && p.enough)) a = p.rnd[i];
   p.a[i] = a;
   if (p.act == nullptr) return;
-  // ExecutionTask.actions, as mxa_ddqn_actions: table[a], or on the horizon's last step the whole
-  // remaining quantity at allocation (1, 0); x / q0 as PyTorch divides by a Python scalar
-  const double* tb = p.table + 3 * a;
-  const double* o = p.obs + (size_t)i * p.obs_w;
-  const bool last = o[0] == 1.0;
-  p.act[3 * (size_t)i] = last ? o[1] * (1.0 / p.q0) : tb[0];
-  p.act[3 * (size_t)i + 1] = last ? 1.0 : tb[1];
-  p.act[3 * (size_t)i + 2] = last ? 0.0 : tb[2];
+  // ExecutionTask.actions, as mxa_ddqn_actions
+  action_of(p.table + 3 * a, p.obs + (size_t)i * p.obs_w, p.q0, p.act + 3 * (size_t)i);
 }
 
 // fills the layer table; false when the dimensions are outside what the kernel supports

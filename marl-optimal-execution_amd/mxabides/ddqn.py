@@ -202,8 +202,8 @@ class DDQNLearner:
     `learn_step_counter`) a no-op when it is false, without a host read. The counter and epsilon
     are device scalars for the same reason.
 
-    `fused_act` (include/mxa_qnet.h): every forward without a gradient (q_values, and so
-    choose_action and act; q_target's target(s2) and eval(s)) runs in libmxa_qnet.so's kernel,
+    `fused_act` (include/mxa_ddqn.h mxa_qnet_*): every forward without a gradient (q_values, and so
+    choose_action and act; q_target's target(s2) and eval(s)) runs in libmxa_ddqn.so's kernel,
     and choose_action / act make the forward, the argmax and the epsilon-greedy select one launch.
     The exploration draws are the same two torch calls, so the stream `gen` and every exploring
     env's action are unchanged; Q-values differ from hipBLASLt's in the last bits (another
@@ -217,10 +217,10 @@ class DDQNLearner:
                  fused_act=None):
         self.device = torch.device(device)
         self.dtype = dtype
-        can_fuse = self.device.type == "cuda" and dtype == torch.float32 and qnet_lib() is not None
+        can_fuse = self.device.type == "cuda" and dtype == torch.float32 and lib() is not None
         if fused_act and not can_fuse:
-            raise RuntimeError("DDQNLearner(fused_act=True) needs a CUDA device, dtype float32 and libmxa_qnet.so "
-                               "(build_lib.build_qnet)")
+            raise RuntimeError("DDQNLearner(fused_act=True) needs a CUDA device, dtype float32 and libmxa_ddqn.so "
+                               "(build_lib.build_ddqn)")
         if fused_act is None:
             fused_act = os.environ.get("MXA_DDQN_FUSED_ACT") == "1" and can_fuse
         self.fused_act = bool(fused_act)
@@ -311,22 +311,28 @@ class DDQNLearner:
                 for w in self.eval_model.dropout_widths()]
 
     # ---- acting (choose_action, :333-362)
-    def _qnet_forward(self, flat, s):
-        """mxa_qnet_forward of the net whose parameters are `flat` (eflat or tflat)"""
+    def _predict(self, net, flat, s):
+        """Keras predict (training=False: no dropout, no gradient) of eval_model / eflat or
+        target_model / tflat; with fused_act in one launch (mxa_qnet_forward)"""
+        if not self.fused_act:
+            net.eval()
+            with torch.no_grad():
+                return net(s.to(self.dtype))
         x = s.detach().to(torch.float32).contiguous()
         q = torch.empty((x.shape[0], self.n_actions), dtype=torch.float32, device=self.device)
-        rc = qnet_lib().mxa_qnet_forward(torch.cuda.current_stream().cuda_stream, x.shape[0], x.data_ptr(),
-                                         flat.data_ptr(), len(self._qdims) - 1, self._qdims, q.data_ptr())
-        if rc:
-            raise RuntimeError("mxa_qnet_forward: hip error %d" % rc)
+        _call("mxa_qnet_forward", x.shape[0], x.data_ptr(), flat.data_ptr(), len(self._qdims) - 1, self._qdims,
+              q.data_ptr())
         return q
 
     def q_values(self, s):
-        if self.fused_act:
-            return self._qnet_forward(self.eflat, s)
-        self.eval_model.eval()  # Keras predict(): training=False, no dropout
-        with torch.no_grad():
-            return self.eval_model(s.to(self.dtype))
+        return self._predict(self.eval_model, self.eflat, s)
+
+    def _explore(self, n):
+        """choose_action's exploration draws from `gen`: U [n] float64, the random actions [n],
+        and whether the replay holds enough experience to exploit (len + 1 > batch_size)"""
+        u = torch.rand(n, generator=self.gen, device=self.device, dtype=torch.float64)
+        rnd = torch.randint(0, self.n_actions, (n,), generator=self.gen, device=self.device)
+        return u, rnd, self.memory.more_than(self.batch_size - 1)
 
     def act(self, s, obs=None, task=None, out_a=None, out_act=None):
         """fused_act only: choose_action(s) and, with `obs` and `task`, ExecutionTask.actions of
@@ -355,54 +361,36 @@ class DDQNLearner:
             obs_w, obs_p, tab_p, act_p, q0 = obs.shape[1], obs.data_ptr(), table.data_ptr(), out_act.data_ptr(), task.q0
         if out_a.dtype != torch.int64 or tuple(out_a.shape) != (n,) or not out_a.is_contiguous():
             raise ValueError("act: out_a must be a contiguous int64 [n] tensor")
-        u = rnd = None
-        enough = False
-        if not test:  # the same draws, in the same order, as the unfused choose_action
-            u = torch.rand(n, generator=self.gen, device=self.device, dtype=torch.float64)
-            rnd = torch.randint(0, self.n_actions, (n,), generator=self.gen, device=self.device)
-            enough = self.memory.more_than(self.batch_size - 1)  # len + 1 > batch_size
-        rc = qnet_lib().mxa_qnet_act(torch.cuda.current_stream().cuda_stream, n, x.data_ptr(), self.eflat.data_ptr(),
-                                     len(self._qdims) - 1, self._qdims, int(test), int(enough),
-                                     None if test else u.data_ptr(), None if test else rnd.data_ptr(),
-                                     self._eps.data_ptr(), obs_w, obs_p, tab_p, q0, out_a.data_ptr(), act_p, None)
-        if rc:
-            raise RuntimeError("mxa_qnet_act: hip error %d" % rc)
+        u, rnd, enough = (None, None, False) if test else self._explore(n)  # the unfused choose_action's draws
+        _call("mxa_qnet_act", n, x.data_ptr(), self.eflat.data_ptr(), len(self._qdims) - 1, self._qdims, int(test),
+              int(enough), None if test else u.data_ptr(), None if test else rnd.data_ptr(), self._eps.data_ptr(),
+              obs_w, obs_p, tab_p, q0, out_a.data_ptr(), act_p, None)
         return out_a, out_act
 
     def choose_action(self, s):
         """s [n, n_state] -> actions [n] int64 (epsilon-greedy per env in train mode)."""
         if self.fused_act:
             return self.act(s)[0]
-        n = s.shape[0]
         greedy = torch.argmax(self.q_values(s), dim=1)
         if self.mode == "test":
             return greedy
-        u = torch.rand(n, generator=self.gen, device=self.device, dtype=torch.float64)
-        rnd = torch.randint(0, self.n_actions, (n,), generator=self.gen, device=self.device)
-        exploit = (u < self._eps) & self.memory.more_than(self.batch_size - 1)  # len + 1 > batch_size
-        return torch.where(exploit, greedy, rnd)
+        u, rnd, enough = self._explore(s.shape[0])
+        return torch.where((u < self._eps) & enough, greedy, rnd)
 
     # ---- learning (train_neural_nets, :448-515)
     def q_target(self, s, a, s2, r):
         """the reference's target: both q_next and q_eval4next from the target net (:486-505)."""
-        if self.fused_act:  # the two forwards of the target net are one and the same: computed once
-            q_next = self._qnet_forward(self.tflat, s2)
-            tgt = self._qnet_forward(self.eflat, s)
-            idx = torch.arange(s.shape[0], device=self.device)
-            best = torch.argmax(q_next, dim=1)
-            tgt[idx, a] = r.to(self.dtype) + self.reward_decay * q_next[idx, best]
-            return tgt
-        self.target_model.eval()
-        self.eval_model.eval()
         with torch.no_grad():
-            s, s2, r = s.to(self.dtype), s2.to(self.dtype), r.to(self.dtype)
-            q_next = self.target_model(s2)
-            q_eval4next = self.target_model(s2)
-            q_eval = self.eval_model(s)
-            tgt = q_eval.clone()
-            idx = torch.arange(s.shape[0], device=s.device)
+            q_next = self._predict(self.target_model, self.tflat, s2)
+            # the reference's second forward of the target net; the kernel's result is bitwise the
+            # same in any batch, so with fused_act it is computed once
+            q_eval4next = q_next if self.fused_act else self._predict(self.target_model, self.tflat, s2)
+            tgt = self._predict(self.eval_model, self.eflat, s)
+            if not self.fused_act:
+                tgt = tgt.clone()  # q_eval.copy() (:490); the kernel's output is a buffer of its own already
+            idx = torch.arange(s.shape[0], device=self.device)
             best = torch.argmax(q_eval4next, dim=1)
-            tgt[idx, a] = r + self.reward_decay * q_next[idx, best]
+            tgt[idx, a] = r.to(self.dtype) + self.reward_decay * q_next[idx, best]
         return tgt
 
     def learn_on(self, s, a, s2, r, live=None, masks=None):
@@ -526,112 +514,144 @@ class ExecutionTask:
         return torch.where(dq > 0, 1e4 / q0 * (2 * dq + dcash / arrival), torch.zeros_like(dq))
 
 
-_PERIOD_LIB = None
+_LIB = None
 
 
-def period_lib():
-    """libmxa_ddqn.so (include/mxa_ddqn.h): the per-period bookkeeping kernel of run_episode;
-    None when it is not built"""
-    global _PERIOD_LIB
-    if _PERIOD_LIB is None:
-        import ctypes
+def lib():
+    """libmxa_ddqn.so (include/mxa_ddqn.h) as a ctypes.CDLL with every export's argtypes set: the
+    per-period kernels of run_episode and the Q-network forward and epsilon-greedy action kernel of
+    DDQNLearner(fused_act=True); None when it is not built"""
+    global _LIB
+    if _LIB is None:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "libmxa_ddqn.so")
         if not os.path.exists(path):
             return None
         L = ctypes.CDLL(path)
-        P, I, I64, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
+        P, I, I64, D, DIMS = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.POINTER(ctypes.c_int)
         L.mxa_ddqn_period.argtypes = [P, I, I, I, I] + [P] * 13 + [P, I, P, I, D, D, D, P, P, P, P, I64, P, P]
         L.mxa_ddqn_state.argtypes = [P, I, I, P, P, I, P, I, D, D, P]
         L.mxa_ddqn_actions.argtypes = [P, I, I, P, P, P, D, P]
-        _PERIOD_LIB = L
-    return _PERIOD_LIB
+        L.mxa_qnet_forward.argtypes = [P, I, P, P, I, DIMS, P]
+        L.mxa_qnet_act.argtypes = [P, I, P, P, I, DIMS, I, I, P, P, P, I, P, P, D, P, P, P]
+        _LIB = L
+    return _LIB
 
 
-_QNET_LIB = None
+period_lib = lib  # the name bench.py asks by
+qnet_lib = lib  # the Q-network exports' loader by its earlier name, for callers that predate lib()
 
 
-def qnet_lib():
-    """libmxa_qnet.so (include/mxa_qnet.h): the Q-network forward and epsilon-greedy action kernel
-    of DDQNLearner(fused_act=True); None when it is not built"""
-    global _QNET_LIB
-    if _QNET_LIB is None:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "libmxa_qnet.so")
-        if not os.path.exists(path):
-            return None
-        L = ctypes.CDLL(path)
-        P, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-        L.mxa_qnet_forward.argtypes = [P, I, P, P, I, ctypes.POINTER(I), P]
-        L.mxa_qnet_act.argtypes = [P, I, P, P, I, ctypes.POINTER(I), I, I, P, P, P, I, P, P, D, P, P, P]
-        _QNET_LIB = L
-    return _QNET_LIB
-
-
-def _state_device(L, task, obs, out):
-    rc = L.mxa_ddqn_state(torch.cuda.current_stream().cuda_stream, obs.shape[0], obs.shape[1], obs.data_ptr(),
-                          task.grid[0].data_ptr(), task.grid[0].numel(), task.grid[1].data_ptr(), task.grid[1].numel(),
-                          float(task.nh), task.q0, out.data_ptr())
+def _call(name, *args):
+    """the export `name` of lib() on the current torch stream; a hipError_t raises"""
+    rc = getattr(lib(), name)(torch.cuda.current_stream().cuda_stream, *args)
     if rc:
-        raise RuntimeError("mxa_ddqn_state: hip error %d" % rc)
+        raise RuntimeError("%s: hip error %d" % (name, rc))
+
+
+def _state_device(task, obs, out):
+    _call("mxa_ddqn_state", obs.shape[0], obs.shape[1], obs.data_ptr(), task.grid[0].data_ptr(), task.grid[0].numel(),
+          task.grid[1].data_ptr(), task.grid[1].numel(), float(task.nh), task.q0, out.data_ptr())
     return out
+
+
+def _act(learner, task, s, obs, out):
+    """the period's actions a [n] and their action vectors [n, 3] (ExecutionTask.actions). `out` is
+    the kernels' action-vector buffer; None: PyTorch ops, which make a new one"""
+    if out is not None and learner.fused_act:  # forward, epsilon-greedy select and action vector in one launch
+        return learner.act(s, obs, task, out_act=out)
+    a = learner.choose_action(s)
+    if out is None:
+        return a, task.actions(a, obs)
+    a = a.contiguous()
+    _call("mxa_ddqn_actions", obs.shape[0], obs.shape[1], obs.data_ptr(), a.data_ptr(),
+          task.table.contiguous().data_ptr(), task.q0, out.data_ptr())
+    return a, out
+
+
+def period_torch(task, m, train, obs, st, prev, arrival, flags, alive, s, a, env_steps, stored, r_row, spare=None):
+    """One period's bookkeeping after the env step, as PyTorch ops: ok = alive & obs valid & no env
+    error; the reward of the step's fills from the agent states `prev` and `st`; the next state
+    s2; env_steps += alive; with `train` the ok envs' transitions (s, a, s2, r) appended to the
+    replay ring `m` and counted in `stored`; r_row = where(ok, r, 0). Returns s2, the next alive
+    mask and any(alive), the learner's update mask (the reference's agents stop training with their
+    episode), all left on the device. `spare` is unused: period_kernel's output buffers."""
+    ok = alive & ((flags & 2) != 0) & ((flags & 4) == 0)
+    r = task.reward(prev, st, arrival, task.q0)
+    s2 = task.state(obs)
+    env_steps += alive.to(torch.int64)
+    if train:
+        stored += m.add_device(s, a, s2, r, ok)
+    torch.where(ok, r, torch.zeros_like(r), out=r_row)
+    return s2, ok & ((flags & 1) == 0), alive.any()
+
+
+def period_kernel(task, m, train, obs, st, prev, arrival, flags, alive, s, a, env_steps, stored, r_row, spare):
+    """period_torch in one launch (include/mxa_ddqn.h mxa_ddqn_period), bitwise the same; s2, the
+    next alive mask and the update mask are written into the three buffers of `spare` and returned.
+    The kernel refuses a training batch of more envs than the replay capacity."""
+    s2, alive_next, live = spare
+    g0, g1 = task.grid
+    n = obs.shape[0]
+    _call("mxa_ddqn_period", n, obs.shape[1], st.shape[1], int(train), obs.data_ptr(), st.data_ptr(), prev.data_ptr(),
+          arrival.data_ptr(), flags.data_ptr(), alive.data_ptr(), alive_next.data_ptr(), live.data_ptr(), s.data_ptr(),
+          a.data_ptr(), s2.data_ptr(), r_row.data_ptr(), env_steps.data_ptr(), g0.data_ptr(), g0.numel(), g1.data_ptr(),
+          g1.numel(), float(task.nh), task.q0, 1e4 / task.q0, m.s.data_ptr(), m.s2.data_ptr(), m.a.data_ptr(),
+          m.r.data_ptr(), m.cap, m.n_dev.data_ptr(), stored.data_ptr())
+    if train:
+        m.n_ub += n
+    return spare
 
 
 def run_episode(env, learner, task, seeds=None, train_every=5, updates_per_train=1, record=None, timing=None,
                 fused=None):
-    """fused (default: a learner on the GPU with libmxa_ddqn.so built): the bookkeeping after each
-    step in one kernel (include/mxa_ddqn.h), bitwise the same as the PyTorch ops that fused=False
-    runs (tests/test_gpu_ddqn.py; 59.9 -> 55.8 ms per rmsc03_ddqn x4096 episode on one box); both
-    equal the plain float64 references of oracle/ddqn_ref.py (tests/test_gpu_ddqn_kernels.py).
-    The kernel refuses a training batch of more envs than the replay capacity."""
-    L = period_lib() if fused is not False and learner.device.type == "cuda" else None
-    if fused and L is None:
-        raise RuntimeError("run_episode(fused=True): libmxa_ddqn.so is not built (build_lib.build_ddqn)")
-    if L is not None:
-        return _run_episode_fused(L, env, learner, task, seeds, train_every, updates_per_train, record, timing)
-    return _run_episode_torch(env, learner, task, seeds, train_every, updates_per_train, record, timing)
+    """One episode of every env of a VecABIDESEnv (rmsc03 + DummyRL) driven by the learner, all on
+    the current torch stream (the env must step on it: env.set_stream). Mirrors the agent's
+    per-period loop (place_order, :275-299): observe, choose, act, then store the completed
+    transition and train every `train_every` periods (train_step_counter % 5 == 0, :286-293).
+    Every horizon step is enqueued without waiting for the GPU: envs that are done stay done in the
+    step kernel, their rows are masked out, and an update once every env is done is a masked no-op.
 
+    fused (default: a learner on the GPU with libmxa_ddqn.so built): the action vectors and the
+    bookkeeping after each step in one kernel each (period_kernel), bitwise the same as the PyTorch
+    ops that fused=False runs (period_torch; tests/test_gpu_ddqn.py; 59.9 -> 55.8 ms per
+    rmsc03_ddqn x4096 episode on one box); both equal the plain float64 references of
+    oracle/ddqn_ref.py (tests/test_gpu_ddqn_kernels.py, tests/test_ddqn_episode.py).
 
-def _run_episode_fused(L, env, learner, task, seeds, train_every, updates_per_train, record, timing):
-    """run_episode with the per-period bookkeeping in one launch; same order of RNG draws, replay
-    appends and updates as _run_episode_torch"""
+    Returns a dict of device tensors (rewards [steps, n], actions [steps, n], flags) and the
+    number of stored transitions. `record` (a list) receives the per-step action vectors;
+    `timing` (a list) receives a (start, end) torch.cuda.Event pair around every step launch."""
     from .gym import OBS_SIZE, RL_STATE_WORDS
-    dev = learner.device
-    n = env.n_envs
-    nh = task.nh
+    kernel = fused is not False and learner.device.type == "cuda" and lib() is not None
+    if fused and not kernel:
+        raise RuntimeError("run_episode(fused=True): libmxa_ddqn.so is not built (build_lib.build_ddqn)")
+    period = period_kernel if kernel else period_torch
+    dev, n, nh = learner.device, env.n_envs, task.nh
     env.reset(seeds=seeds)
     obs = torch.zeros((n, OBS_SIZE), dtype=torch.float64, device=dev)
     flags = torch.zeros(n, dtype=torch.int32, device=dev)
     st = torch.zeros((n, RL_STATE_WORDS), dtype=torch.float64, device=dev)
     prev = torch.zeros_like(st)
-    act0 = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+    act0 = torch.zeros((n, 3), dtype=torch.float64, device=dev)  # first step: no cached LOB, nothing placed
     env.step_device(act0.data_ptr(), obs.data_ptr(), flags.data_ptr())
     env.write_rl_state(st.data_ptr())
     if record is not None:
         record.append(act0.clone())
     alive = ((flags & 2) != 0) & ((flags & 5) == 0)
-    alive_next = torch.zeros_like(alive)
-    live = torch.zeros((), dtype=torch.bool, device=dev)
     lob_ok = (st[:, 7] == 3)
-    arrival = torch.where(lob_ok, (st[:, 3] + st[:, 4]) / 2, torch.ones_like(st[:, 3])).contiguous()
+    arrival = torch.where(lob_ok, (st[:, 3] + st[:, 4]) / 2, torch.ones_like(st[:, 3])).contiguous()  # mid at start_time
     rw = torch.zeros((nh, n), dtype=torch.float64, device=dev)
     actions = []
     stored = torch.zeros((), dtype=torch.int64, device=dev)
-    env_steps = alive.to(torch.int64)
-    s = _state_device(L, task, obs, torch.empty((n, 2), dtype=torch.float32, device=dev))
-    s2 = torch.empty_like(s)
-    m = learner.memory
+    env_steps = alive.to(torch.int64)  # per env: ABIDESEnv.step calls taken while alive (the first one included)
+    if kernel:  # the kernels fill preallocated buffers: the action vectors, and (s2, alive_next, live)
+        s = _state_device(task, obs, torch.empty((n, 2), dtype=torch.float32, device=dev))
+        out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        spare = (torch.empty_like(s), torch.zeros_like(alive), torch.zeros((), dtype=torch.bool, device=dev))
+    else:
+        s, out, spare = task.state(obs), None, None
     train = learner.mode == "train"
-    g0, g1 = task.grid
-    table = task.table.contiguous()
-    act = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    for step_counter in range(nh):
-        if learner.fused_act:  # forward, epsilon-greedy select and action vector in one launch
-            a, _ = learner.act(s, obs, task, out_act=act)
-        else:
-            a = learner.choose_action(s).contiguous()
-            rc = L.mxa_ddqn_actions(torch.cuda.current_stream().cuda_stream, n, obs.shape[1], obs.data_ptr(),
-                                    a.data_ptr(), table.data_ptr(), task.q0, act.data_ptr())
-            if rc:
-                raise RuntimeError("mxa_ddqn_actions: hip error %d" % rc)
+    for t in range(nh):
+        a, act = _act(learner, task, s, obs, out)
         if record is not None:
             record.append(act.clone())
         st, prev = prev, st  # write_rl_state fills the other buffer: prev keeps the state before the step
@@ -643,93 +663,13 @@ def _run_episode_fused(L, env, learner, task, seeds, train_every, updates_per_tr
             e1.record()
             timing.append((e0, e1))
         env.write_rl_state(st.data_ptr())
-        rc = L.mxa_ddqn_period(torch.cuda.current_stream().cuda_stream, n, obs.shape[1], st.shape[1], int(train),
-                               obs.data_ptr(), st.data_ptr(), prev.data_ptr(), arrival.data_ptr(), flags.data_ptr(),
-                               alive.data_ptr(), alive_next.data_ptr(), live.data_ptr(), s.data_ptr(), a.data_ptr(),
-                               s2.data_ptr(), rw[step_counter].data_ptr(), env_steps.data_ptr(), g0.data_ptr(),
-                               g0.numel(), g1.data_ptr(), g1.numel(), float(nh), task.q0, 1e4 / task.q0,
-                               m.s.data_ptr(), m.s2.data_ptr(), m.a.data_ptr(), m.r.data_ptr(), m.cap,
-                               m.n_dev.data_ptr(), stored.data_ptr())
-        if rc:
-            raise RuntimeError("mxa_ddqn_period: hip error %d" % rc)
-        if train:
-            m.n_ub += n
-            if step_counter % train_every == 0:
-                for _ in range(updates_per_train):
-                    learner.learn(live=live)
+        s2, alive_next, live = period(task, learner.memory, train, obs, st, prev, arrival, flags, alive, s, a,
+                                      env_steps, stored, rw[t], spare)
+        if train and t % train_every == 0:
+            for _ in range(updates_per_train):
+                learner.learn(live=live)
         actions.append(a)
-        alive, alive_next = alive_next, alive
-        s, s2 = s2, s
+        s, alive, spare = s2, alive_next, (s, alive, live)  # the buffers of the period before are free again
     return {"rewards": rw if nh else None, "actions": torch.stack(actions) if actions else None,
             "returns": rw.sum(0), "flags": flags, "arrival": arrival, "stored": stored, "env_steps": env_steps,
             "steps": nh + 1}
-
-
-def _run_episode_torch(env, learner, task, seeds=None, train_every=5, updates_per_train=1, record=None, timing=None):
-    """One episode of every env of a VecABIDESEnv (rmsc03 + DummyRL) driven by the learner, all on
-    the current torch stream (the env must step on it: env.set_stream). Mirrors the agent's
-    per-period loop (place_order, :275-299): observe, choose, act, then store the completed
-    transition and train every `train_every` periods (train_step_counter % 5 == 0, :286-293).
-
-    Returns a dict of device tensors (rewards [steps, n], actions [steps, n], flags) and the
-    number of stored transitions. `record` (a list) receives the per-step action vectors;
-    `timing` (a list) receives a (start, end) torch.cuda.Event pair around every step launch."""
-    from .gym import OBS_SIZE, RL_STATE_WORDS
-    dev = learner.device
-    n = env.n_envs
-    nh = task.nh
-    env.reset(seeds=seeds)
-    obs = torch.zeros((n, OBS_SIZE), dtype=torch.float64, device=dev)
-    flags = torch.zeros(n, dtype=torch.int32, device=dev)
-    st = torch.zeros((n, RL_STATE_WORDS), dtype=torch.float64, device=dev)
-    act0 = torch.zeros((n, 3), dtype=torch.float64, device=dev)  # first step: no cached LOB, nothing placed
-    env.step_device(act0.data_ptr(), obs.data_ptr(), flags.data_ptr())
-    env.write_rl_state(st.data_ptr())
-    if record is not None:
-        record.append(act0.clone())
-    alive = ((flags & 2) != 0) & ((flags & 5) == 0)
-    lob_ok = (st[:, 7] == 3)
-    arrival = torch.where(lob_ok, (st[:, 3] + st[:, 4]) / 2, torch.ones_like(st[:, 3]))  # mid at start_time
-    rewards, actions = [], []
-    stored = torch.zeros((), dtype=torch.int64, device=dev)
-    env_steps = alive.to(torch.int64)  # per env: ABIDESEnv.step calls taken while alive (the first one included)
-    step_counter = 0
-    # every horizon step is enqueued without waiting for the GPU (no host read of `alive` except
-    # on training steps): envs that are done stay done in the step kernel, and their rows are
-    # masked out below
-    for _ in range(nh):
-        s = task.state(obs)
-        a = learner.choose_action(s)
-        act = task.actions(a, obs)
-        if record is not None:
-            record.append(act.clone())
-        prev = st.clone()
-        if timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        env.step_device(act.data_ptr(), obs.data_ptr(), flags.data_ptr())
-        if timing is not None:
-            e1.record()
-            timing.append((e0, e1))
-        env.write_rl_state(st.data_ptr())
-        ok = alive & ((flags & 2) != 0) & ((flags & 4) == 0)
-        r = task.reward(prev, st, arrival, task.q0)
-        s2 = task.state(obs)
-        env_steps += alive.to(torch.int64)
-        if learner.mode == "train":
-            stored += learner.memory.add_device(s, a, s2, r, ok)
-            # the reference's agents stop training with their episode: no update on stale replay
-            # once every env is done; decided on the device (a masked no-op), no host read
-            if step_counter % train_every == 0:
-                live = alive.any()
-                for _ in range(updates_per_train):
-                    learner.learn(live=live)
-        rewards.append(torch.where(ok, r, torch.zeros_like(r)))
-        actions.append(a)
-        step_counter += 1
-        alive = ok & ((flags & 1) == 0)
-    rw = torch.stack(rewards) if rewards else None
-    return {"rewards": rw, "actions": torch.stack(actions) if actions else None,
-            "returns": rw.sum(0) if rw is not None else torch.zeros(n, dtype=torch.float64, device=dev),
-            "flags": flags, "arrival": arrival, "stored": stored, "env_steps": env_steps,
-            "steps": step_counter + 1}

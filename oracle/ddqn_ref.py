@@ -106,7 +106,7 @@ def train_step(eval_layers, target_layers, rms, counter, batch, lr=0.01, gamma=0
     return eval_layers, target_layers, rms, counter + 1, loss
 
 
-# ---- plain references of the device kernels (include/mxa_ddqn.h, include/mxa_qnet.h).  float64
+# ---- plain references of the device kernels (include/mxa_ddqn.h).  float64
 # IEEE arithmetic, one rounding per operation, nothing taken from the code under test: the kernels'
 # tests compare with exact equality.
 
@@ -226,6 +226,6 @@ def integer_net(dims, n_rows, seed, nnz=None):
 
 
 def flat_params(layers):
-    """the flat float32 parameter buffer of include/mxa_qnet.h: per layer weight[out][in]
+    """the flat float32 parameter buffer of include/mxa_ddqn.h mxa_qnet_*: per layer weight[out][in]
     row-major, then bias[out]"""
     return np.concatenate([np.concatenate([W.T.reshape(-1), b]) for W, b in layers]).astype(np.float32)

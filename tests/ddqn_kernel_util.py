@@ -148,11 +148,13 @@ def make_task(c, device):
 
 
 def torch_period(c, device):
-    """the period as run_episode's PyTorch ops (mxabides.ddqn._run_episode_torch) on `device`;
-    returns the outputs as numpy. The ring's spare row `cap` takes the masked-out rows of
+    """the period as run_episode's PyTorch ops (mxabides.ddqn.period_torch) on `device`; returns
+    the outputs as numpy. The ring's spare row `cap` takes the masked-out rows of
     ReplayRing.add_device here, so it is returned but not comparable with the kernel's."""
     dv = lambda k: torch.from_numpy(np.ascontiguousarray(c[k])).to(device)
     task = make_task(c, device)
+    task.q0 = c["q0_reward"]  # the reward's scale alone: the state divides by the tensor task._q0
+    assert float(task._q0) == c["q0"], "ExecutionTask.state no longer has a quantity of its own"
     obs, st, prev, arrival, flags, alive = (dv(k).reshape(np.shape(c[k])) for k in
                                             ("obs", "st", "prev", "arrival", "flags", "alive"))
     s, a, env_steps = dv("s"), dv("a"), dv("env_steps").clone()
@@ -160,15 +162,11 @@ def torch_period(c, device):
     m.s, m.s2, m.a, m.r = dv("ring_s").clone(), dv("ring_s2").clone(), dv("ring_a").clone(), dv("ring_r").clone()
     m.n_dev = torch.tensor(c["n_dev"], dtype=torch.int64, device=device)
     stored = torch.tensor(c["stored"], dtype=torch.int64, device=device)
-    ok = alive & ((flags & 2) != 0) & ((flags & 4) == 0)
-    r = task.reward(prev, st, arrival, c["q0_reward"])
-    s2 = task.state(obs)
-    env_steps += alive.to(torch.int64)
-    if c["train"]:
-        stored += m.add_device(s, a, s2, r, ok)
-    out = {"alive_next": ok & ((flags & 1) == 0), "live": alive.any(), "s2": s2, "r_row": torch.where(ok, r, torch.zeros_like(r)),
-           "env_steps": env_steps, "ring_s": m.s, "ring_s2": m.s2, "ring_a": m.a, "ring_r": m.r, "n_dev": m.n_dev,
-           "stored": stored}
+    r_row = torch.empty(c["n"], dtype=torch.float64, device=device)
+    s2, alive_next, live = ddqn.period_torch(task, m, c["train"], obs, st, prev, arrival, flags, alive, s, a, env_steps,
+                                             stored, r_row)
+    out = {"alive_next": alive_next, "live": live, "s2": s2, "r_row": r_row, "env_steps": env_steps, "ring_s": m.s,
+           "ring_s2": m.s2, "ring_a": m.a, "ring_r": m.r, "n_dev": m.n_dev, "stored": stored}
     out = {k: v.cpu().numpy() for k, v in out.items()}
     for k in ("live", "n_dev", "stored"):
         out[k] = out[k].item()

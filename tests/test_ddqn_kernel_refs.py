@@ -177,7 +177,7 @@ def _period_guard(L, n=4, obs_w=9, st_w=8, train=1, cap=16):
 
 def test_ddqn_library_guards_return_before_any_hip_call():
     """null pointers and no device: each refused call returns hipErrorInvalidValue"""
-    L = ddqn.period_lib()
+    L = ddqn.lib()
     assert L is not None, "libmxa_ddqn.so not built (build_lib.build_ddqn)"
     assert _period_guard(L, n=-1) == HIP_ERROR_INVALID_VALUE
     assert _period_guard(L, cap=0) == HIP_ERROR_INVALID_VALUE

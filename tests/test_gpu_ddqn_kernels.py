@@ -1,5 +1,5 @@
 """include/mxa_ddqn.h on the GPU, kernel by kernel: mxa_ddqn_period, mxa_ddqn_state and
-mxa_ddqn_actions called through ddqn.period_lib() on synthetic device buffers, at the sizes and
+mxa_ddqn_actions called through ddqn.lib() on synthetic device buffers, at the sizes and
 inputs where they can go wrong (a second and third 1024-env block, full and single-lane waves, a
 ring that wraps, train off, other row widths and grids, NaN / inf, every remaining quantity).
 Every output is compared with exact equality against the plain float64 references of
@@ -19,7 +19,7 @@ Guarded = U.Guarded
 
 
 def _lib():
-    L = ddqn.period_lib()
+    L = ddqn.lib()
     assert L is not None, "libmxa_ddqn.so not built (build_lib.build_ddqn)"
     return L
 

@@ -1,5 +1,5 @@
-"""include/mxa_qnet.h on the GPU: the hand-written Q-network forward and epsilon-greedy action
-kernel (libmxa_qnet.so, DDQNLearner(fused_act=True)) against an fp64 forward of the same weights,
+"""include/mxa_ddqn.h mxa_qnet_* on the GPU: the hand-written Q-network forward and epsilon-greedy action
+kernel (libmxa_ddqn.so, DDQNLearner(fused_act=True)) against an fp64 forward of the same weights,
 over the whole 200 x 200 state space, and the learner paths built on it; then the kernel's edges
 (odd widths, both staging paths, all of its LDS, every output of mxa_qnet_act, the select's and
 the argmax's branches) with exact equality against oracle/ddqn_ref.py."""
@@ -52,7 +52,7 @@ def _ref(model):
 def _forward_raw(flat, dims, x, q_ptr, stream=None):
     d = (ctypes.c_int * len(dims))(*dims)
     st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    rc = ddqn.qnet_lib().mxa_qnet_forward(st, x.shape[0], x.data_ptr(), flat.data_ptr(), len(dims) - 1, d, q_ptr)
+    rc = ddqn.lib().mxa_qnet_forward(st, x.shape[0], x.data_ptr(), flat.data_ptr(), len(dims) - 1, d, q_ptr)
     assert rc == 0, rc
 
 
@@ -291,7 +291,7 @@ def _fwd(flat, dims, x, what):
     """mxa_qnet_forward on x (numpy), q behind sentinels"""
     xg = U.Guarded(x.astype(np.float32))
     q = U.Guarded(np.full((len(x), dims[-1]), -3.0, dtype=np.float32))
-    rc = ddqn.qnet_lib().mxa_qnet_forward(torch.cuda.current_stream().cuda_stream, len(x), xg.ptr, flat.data_ptr(),
+    rc = ddqn.lib().mxa_qnet_forward(torch.cuda.current_stream().cuda_stream, len(x), xg.ptr, flat.data_ptr(),
                                           len(dims) - 1, _cdims(dims), q.ptr)
     assert rc == 0, (what, rc)
     torch.cuda.synchronize()
@@ -311,7 +311,7 @@ def _act(flat, dims, x, test, enough, u, rnd, eps, obs, table, q0, what):
     a = U.Guarded(np.full(n, -3, dtype=np.int64))
     act = None if obs is None else U.Guarded(np.full((n, 3), -3.0))
     ptr = lambda g: None if g is None else g.ptr
-    rc = ddqn.qnet_lib().mxa_qnet_act(torch.cuda.current_stream().cuda_stream, n, xg.ptr, flat.data_ptr(), len(dims) - 1,
+    rc = ddqn.lib().mxa_qnet_act(torch.cuda.current_stream().cuda_stream, n, xg.ptr, flat.data_ptr(), len(dims) - 1,
                                       _cdims(dims), int(test), int(enough), ptr(ug), ptr(rg), eg.ptr,
                                       2 if obs is None else obs.shape[1], ptr(og), ptr(tg), q0, a.ptr, ptr(act), q.ptr)
     assert rc == 0, (what, rc)

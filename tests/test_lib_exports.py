@@ -45,14 +45,15 @@ int main() { return 0; }
     subprocess.check_call(["g++", "-std=c++20", "-fsyntax-only", "-I", inc, str(src)])
 
 
-def test_ddqn_period_library_exports():
+def test_ddqn_library_exports():
     """libmxa_ddqn.so (include/mxa_ddqn.h) loads and exports what its header declares"""
     src = open(os.path.join(ROOT, "include", "mxa_ddqn.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     names = sorted(set(re.findall(r"\b(mxa_[a-z_0-9]+)\s*\(", src)))
-    assert names == ["mxa_ddqn_actions", "mxa_ddqn_period", "mxa_ddqn_state"]
+    assert names == ["mxa_ddqn_actions", "mxa_ddqn_period", "mxa_ddqn_state", "mxa_qnet_act", "mxa_qnet_forward"]
     from mxabides import ddqn
-    L = ddqn.period_lib()
+    L = ddqn.lib()
     assert L is not None, "libmxa_ddqn.so not built (build_lib.build_ddqn)"
+    assert ddqn.period_lib() is L
     for n in names:
         assert hasattr(L, n), n
