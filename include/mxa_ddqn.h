@@ -14,7 +14,9 @@
  * Dense layers, ReLU on all but the last, no dropout), the epsilon-greedy choice (choose_action,
  * :333-362) and the action vector (take_action, :364-407), with one launch. fp32 with FMA; every
  * output element is one sum over the layer's inputs in index order, so a row's result is bitwise
- * the same in any batch. */
+ * the same in any batch.
+ *
+ * The update (DDQNLearner(fused_learn=True); ddqn_train.hip) is declared in mxa_ddqn_train.h. */
 #ifndef MXA_DDQN_H
 #define MXA_DDQN_H
 #include <stdint.h>

@@ -91,15 +91,17 @@ def build(force=False, verbose=True, jobs=None):
     return OUT
 
 
-DDQN_SRCS = [os.path.join(HERE, "csrc", f) for f in ("ddqn_period.hip", "ddqn_qnet.hip")]
-DDQN_DEPS = DDQN_SRCS + [os.path.join(HERE, "csrc", "ddqn_device.h"), os.path.abspath(__file__)]
+DDQN_SRCS = [os.path.join(HERE, "csrc", f) for f in ("ddqn_period.hip", "ddqn_qnet.hip", "ddqn_train.hip")]
+DDQN_DEPS = DDQN_SRCS + [os.path.join(HERE, "csrc", "ddqn_device.h"), os.path.join(HERE, "csrc", "ddqn_qnet_device.h"),
+                         os.path.abspath(__file__)]
 DDQN_OUT = os.path.join(HERE, "lib", "libmxa_ddqn.so")
 
 
 def build_ddqn(force=False, verbose=True):
-    """libmxa_ddqn.so (include/mxa_ddqn.h): the DDQN learner's kernels (mxabides.ddqn), the per-period
-    bookkeeping of run_episode and the Q-network forward and epsilon-greedy action of
-    DDQNLearner(fused_act=True); a library of its own, outside the engine's build id"""
+    """libmxa_ddqn.so (include/mxa_ddqn.h, mxa_ddqn_train.h): the DDQN learner's kernels (mxabides.ddqn), the
+    per-period bookkeeping of run_episode, the Q-network forward and epsilon-greedy action of
+    DDQNLearner(fused_act=True) and the update of DDQNLearner(fused_learn=True); a library of its own,
+    outside the engine's build id"""
     if not force and os.path.exists(DDQN_OUT) and os.path.getmtime(DDQN_OUT) >= max(map(os.path.getmtime, DDQN_DEPS)):
         return DDQN_OUT
     os.makedirs(os.path.dirname(DDQN_OUT), exist_ok=True)

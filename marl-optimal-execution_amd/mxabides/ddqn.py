@@ -209,12 +209,26 @@ class DDQNLearner:
     env's action are unchanged; Q-values differ from hipBLASLt's in the last bits (another
     summation order). True needs a CUDA device, dtype float32 and the library, else RuntimeError;
     None (the default) turns it on only where the environment has MXA_DDQN_FUSED_ACT=1 and those
-    three hold. train_on_batch's gradient pass stays on autograd."""
+    three hold.
+
+    `fused_learn` (include/mxa_ddqn_train.h): one learn_on update (the Q-target, train_on_batch's
+    training-mode forward with the dropout masks, MSE, the backward pass, the masked target copy,
+    the RMSprop step, epsilon and the counter) is two launches of libmxa_ddqn.so's kernels
+    (mxa_qnet_train) instead of about a hundred on autograd; with a process group the gradient alone
+    (mxa_qnet_grad), the live-weighted all-reduce as before, then mxa_qnet_update. The batch and the
+    masks are drawn by the same torch calls, so `gen_sample` and `gen_drop` are unchanged; the
+    Q-target has fused_act's bits, the gradient is another fp32 summation order of the same terms
+    (each element one sum over the batch in index order, the same bits on every run), and the update
+    has the bits of learn_on's own expressions on that gradient. Independent of fused_act. True
+    needs what fused_act=True needs, and a batch size and net the kernels support (batch <= 256, at
+    most 8 layers of at most 256 units), else RuntimeError; None turns it on only where the
+    environment has MXA_DDQN_FUSED_LEARN=1 and all of that holds. Without it train_on_batch's
+    gradient pass stays on autograd."""
 
     def __init__(self, n_state=2, n_actions=N_ACTIONS, replace_target_iter=5, batch_size=32, learning_rate=0.01,
                  epsilon_increment=None, epsilon_max=0.9, reward_decay=0.98, mode="train", model="NNModel_1",
                  dropout=0.1, capacity=1 << 20, device="cuda", seed=0, dtype=torch.float32, group=None,
-                 fused_act=None):
+                 fused_act=None, fused_learn=None):
         self.device = torch.device(device)
         self.dtype = dtype
         can_fuse = self.device.type == "cuda" and dtype == torch.float32 and lib() is not None
@@ -224,6 +238,9 @@ class DDQNLearner:
         if fused_act is None:
             fused_act = os.environ.get("MXA_DDQN_FUSED_ACT") == "1" and can_fuse
         self.fused_act = bool(fused_act)
+        if fused_learn and not can_fuse:
+            raise RuntimeError("DDQNLearner(fused_learn=True) needs a CUDA device, dtype float32 and libmxa_ddqn.so "
+                               "(build_lib.build_ddqn)")
         self.gen = torch.Generator(device=self.device)  # choose_action's exploration
         self.gen.manual_seed(seed)
         self.gen_sample = torch.Generator(device=self.device)  # train_neural_nets' batch indices
@@ -267,6 +284,19 @@ class DDQNLearner:
             src = dist.get_global_rank(group, 0) if group is not dist.group.WORLD else 0
             dist.broadcast(self.eflat, src, group=group)
             dist.broadcast(self.tflat, src, group=group)
+        # fused_learn: the kernels' workspace and the host array of mask pointers, made once
+        ws_bytes = lib().mxa_qnet_train_workspace(batch_size, len(widths) - 1, self._qdims) if can_fuse else -1
+        if fused_learn and ws_bytes < 0:
+            raise RuntimeError("DDQNLearner(fused_learn=True): batch size %d or widths %s outside what mxa_qnet_train "
+                               "supports (include/mxa_ddqn_train.h)" % (batch_size, widths))
+        if fused_learn is None:
+            fused_learn = os.environ.get("MXA_DDQN_FUSED_LEARN") == "1" and can_fuse and ws_bytes >= 0
+        self.fused_learn = bool(fused_learn)
+        if self.fused_learn:
+            self._ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=self.device)
+            self._mask_ptrs = (ctypes.c_void_p * max(1, len(widths) - 2))()
+            if self.world > 1:
+                self._grad = torch.empty_like(self.eflat)
 
     def _flat(self, net):
         net = net.to(self.device, self.dtype)
@@ -409,6 +439,8 @@ class DDQNLearner:
         local_live = live
         if masks is None:
             masks = self.dropout_masks(s.shape[0])
+        if self.fused_learn:
+            return self._learn_fused(s, a, s2, r, live, masks)
         tgt = self.q_target(s, a, s2, r)
         self.eval_model.train()  # train_on_batch: training=True (dropout active)
         for p in self.eval_model.parameters():
@@ -442,6 +474,49 @@ class DDQNLearner:
         for p in self.eval_model.parameters():
             p.grad = None
         loss = loss.detach()
+        self._record_cost(loss, live)
+        return loss
+
+    def _learn_fused(self, s, a, s2, r, live, masks):
+        """learn_on's update in libmxa_ddqn.so's kernels (include/mxa_ddqn_train.h): one
+        mxa_qnet_train call; with a process group mxa_qnet_grad, the live-weighted all-reduce of
+        learn_on, then mxa_qnet_update on the averaged gradient"""
+        n = s.shape[0]
+        if n != self.batch_size:
+            raise RuntimeError("fused_learn: a batch of %d rows, the workspace is for batch_size %d" % (n, self.batch_size))
+        s = s.detach().to(torch.float32).contiguous()
+        s2 = s2.detach().to(torch.float32).contiguous()
+        r = r.detach().to(torch.float32).contiguous()
+        a = a.to(torch.int64).contiguous()
+        live = live.to(torch.bool)
+        keep = []  # the masks the pointers refer to stay referenced until the call is enqueued
+        for h in range(len(self._mask_ptrs)):
+            m = None if masks is None or h == 0 else masks[h - 1].to(torch.bool).contiguous()
+            keep.append(m)
+            self._mask_ptrs[h] = None if m is None else m.data_ptr()
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        has_inc = self.epsilon_increment is not None
+        net = (len(self._qdims) - 1, self._qdims, self._mask_ptrs, float(self.eval_model.p), float(self.reward_decay),
+               self._ws.data_ptr())
+        upd = (self._counter.data_ptr(), int(self.replace_target_iter), self._eps.data_ptr(), int(has_inc),
+               float(self.epsilon_increment) if has_inc else 0.0, float(self.epsilon_max), float(self.learning_rate),
+               float(self.rho), float(self.rms_eps))
+        if self.world == 1:
+            _call("mxa_qnet_train", n, s.data_ptr(), a.data_ptr(), s2.data_ptr(), r.data_ptr(), self.eflat.data_ptr(),
+                  self.tflat.data_ptr(), *net, None, loss.data_ptr(), None, self.rms.data_ptr(), live.data_ptr(), *upd)
+        else:
+            import torch.distributed as dist
+            g = self._grad
+            _call("mxa_qnet_grad", n, s.data_ptr(), a.data_ptr(), s2.data_ptr(), r.data_ptr(), self.eflat.data_ptr(),
+                  self.tflat.data_ptr(), *net, g.data_ptr(), loss.data_ptr(), None)
+            w = live.to(g.dtype).reshape(1)
+            gl = torch.cat([g * w, w])
+            dist.all_reduce(gl, group=self.group)
+            n_live = gl[-1]
+            live = n_live > 0
+            g = (gl[:-1] / torch.clamp(n_live, min=1)).contiguous()
+            _call("mxa_qnet_update", g.numel(), g.data_ptr(), self.eflat.data_ptr(), self.tflat.data_ptr(),
+                  self.rms.data_ptr(), live.data_ptr(), *upd)
         self._record_cost(loss, live)
         return loss
 
@@ -518,9 +593,10 @@ _LIB = None
 
 
 def lib():
-    """libmxa_ddqn.so (include/mxa_ddqn.h) as a ctypes.CDLL with every export's argtypes set: the
-    per-period kernels of run_episode and the Q-network forward and epsilon-greedy action kernel of
-    DDQNLearner(fused_act=True); None when it is not built"""
+    """libmxa_ddqn.so (include/mxa_ddqn.h, mxa_ddqn_train.h) as a ctypes.CDLL with every export's
+    argtypes set: the per-period kernels of run_episode, the Q-network forward and epsilon-greedy
+    action kernel of DDQNLearner(fused_act=True) and the update kernels of
+    DDQNLearner(fused_learn=True); None when it is not built"""
     global _LIB
     if _LIB is None:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "libmxa_ddqn.so")
@@ -533,6 +609,15 @@ def lib():
         L.mxa_ddqn_actions.argtypes = [P, I, I, P, P, P, D, P]
         L.mxa_qnet_forward.argtypes = [P, I, P, P, I, DIMS, P]
         L.mxa_qnet_act.argtypes = [P, I, P, P, I, DIMS, I, I, P, P, P, I, P, P, D, P, P, P]
+        # include/mxa_ddqn_train.h
+        MASKS = ctypes.POINTER(ctypes.c_void_p)
+        batch = [P, I, P, P, P, P, P, P, I, DIMS, MASKS, D, D, P, P, P, P]
+        update = [P, I, P, I, D, D, D, D, D]  # counter, iter, eps, has_inc, inc, eps_max, lr, rho, rms_eps
+        L.mxa_qnet_train_workspace.argtypes = [I, I, DIMS]
+        L.mxa_qnet_train_workspace.restype = I64
+        L.mxa_qnet_grad.argtypes = batch
+        L.mxa_qnet_update.argtypes = [P, I64, P, P, P, P, P] + update
+        L.mxa_qnet_train.argtypes = batch + [P, P] + update
         _LIB = L
     return _LIB
 
