@@ -99,6 +99,19 @@ constexpr Shape shape(int cfg);
 // obi_rmsc02 307 vs 305 ms, rmsc03 39.4 vs 38.2 ms (ab_dwb_levels.txt), off
 #define MXA_DIRTY_WB_MASK ((1 << 9) | (1 << 10) | (1 << 11) | (1 << 12) | (1 << MXA_CFG_RMSC01) | (1 << MXA_CFG_RMSC02))
 #endif
+// configurations whose POV market maker's once-a-wake exchange queries (QUERY_SPREAD,
+// QUERY_TRANSACTED_VOLUME) and their replies are handled inside the wakeup's own pop when they
+// are the forced next four pops (Eng::mm_cycle, DESIGN.md §3 "Queries answered in place"; bit =
+// config id).  Only the zero-delay, zero-latency configurations qualify at compile time
+// (Eng::SYNCQ); the others compile to the queued path whatever their bit says
+#ifndef MXA_SYNC_QUERY_MASK
+#define MXA_SYNC_QUERY_MASK ((1 << MXA_CFG_RMSC03) | (1 << MXA_CFG_RMSC03_RL))
+#endif
+// ... and whose value agents' wakeups take their CANCEL_ORDER / QUERY_SPREAD round trip the same way
+// (Eng::value_cycle)
+#ifndef MXA_SYNC_VALUE_MASK
+#define MXA_SYNC_VALUE_MASK MXA_SYNC_QUERY_MASK
+#endif
 #ifndef MXA_OPEN_RFD
 #define MXA_OPEN_RFD 128
 #endif

@@ -2169,15 +2169,22 @@ struct Eng {
       h.has_last_update = 1;
     }
   }
-  DEV void cancel_order(const Msg& m) {
-    PROF_SCOPE(67);
+  // OrderBook.cancelOrder's book side: the order leaves the book and `r` is its ORDER_CANCELLED;
+  // false: no such order rests (a silent no-op)
+  DEV bool cancel_book(const Msg& m, Msg& r) {
     int buy = m_buy(m);
     int s = b_find(buy, (i32)m.w[3], (i32)m.w[1]);
-    if (s < 0) return;
+    if (s < 0) return false;
     i32 q = b_get(bq, s), o = b_get(bo, s), mm = b_get(bm, s), p = b_get(bp, s);
     b_free(s);
     if constexpr (BLOG) bl_put(cur, -p, buy ? q : -q);
-    Msg r = msg_order(MK_CANCELLED, o, mm >> 1, mm & 1, q, p, 0);
+    r = msg_order(MK_CANCELLED, o, mm >> 1, mm & 1, q, p, 0);
+    return true;
+  }
+  DEV void cancel_order(const Msg& m) {
+    PROF_SCOPE(67);
+    Msg r;
+    if (!cancel_book(m, r)) return;
     ex_notify(m_agent(m), r);
     if constexpr (MD) {  // OrderBook.py:338
       h.ob_last_update = cur;
@@ -2302,6 +2309,41 @@ struct Eng {
     }
   }
 
+  // the replies to QUERY_SPREAD and QUERY_TRANSACTED_VOLUME (ExchangeAgent.py:217-249): read-only on
+  // the book and the header, shared by ex_receive and the in-place market-maker cycle (mm_cycle)
+  DEV Msg ex_spread_reply(i32 depth, bool closed) {
+    Msg r = msg_make(MK_SPREAD, 0);
+    i32 bb, aa;
+    i64 bqs, aqs;
+    b_inside(bb, aa, bqs, aqs);
+    bool hb = bb != INT32_MIN && depth > 0, ha = aa != INT32_MAX && depth > 0;
+    if (hb) {
+      r.w[1] = (u32)bb;
+      r.w[2] = (u32)bqs;
+    }
+    if (ha) {
+      r.w[3] = (u32)aa;
+      r.w[4] = (u32)aqs;
+    }
+    r.w[5] = (u32)h.last_trade;
+    r.w[0] |= ((u32)hb << 9) | ((u32)ha << 10) | (1u << 11) | ((u32)h.last_trade_float << 8) | ((u32)closed << 7);
+    if constexpr (PW == 8) {  // level counts and level-2 prices (w6/w7 = price2 | count << 20)
+      i32 b2 = 0, a2 = 0;
+      i32 nb = hb ? b_levels(1, bb, depth, b2) : 0, na = ha ? b_levels(0, aa, depth, a2) : 0;
+      if ((u32)b2 >= (1u << 20) || (u32)a2 >= (1u << 20)) fail(ERR_RP_PRICE);
+      r.w[6] = (u32)b2 | ((u32)nb << 20);
+      r.w[7] = (u32)a2 | ((u32)na << 20);
+    }
+    return r;
+  }
+  DEV Msg ex_tv_reply(i64 vol, bool closed) {
+    Msg r = msg_make(MK_TV, 0);
+    r.w[0] |= (1u << 11) | ((u32)closed << 7);
+    r.w[1] = (u32)(u64)vol;
+    r.w[2] = (u32)((u64)vol >> 32);
+    return r;
+  }
+
   // ExchangeAgent.receiveMessage (ExchangeAgent.py:129-340)
   DEV void ex_receive(const Msg& m) {
     PROF_SCOPE(73);
@@ -2357,33 +2399,9 @@ struct Eng {
       ex_notify(sender, r);
       break;
     }
-    case MK_SPREAD_REQ: {
-      i32 depth = (i32)m.w[1];
-      Msg r = msg_make(MK_SPREAD, 0);
-      i32 bb, aa;
-      i64 bqs, aqs;
-      b_inside(bb, aa, bqs, aqs);
-      bool hb = bb != INT32_MIN && depth > 0, ha = aa != INT32_MAX && depth > 0;
-      if (hb) {
-        r.w[1] = (u32)bb;
-        r.w[2] = (u32)bqs;
-      }
-      if (ha) {
-        r.w[3] = (u32)aa;
-        r.w[4] = (u32)aqs;
-      }
-      r.w[5] = (u32)h.last_trade;
-      r.w[0] |= ((u32)hb << 9) | ((u32)ha << 10) | (1u << 11) | ((u32)h.last_trade_float << 8) | ((u32)closed << 7);
-      if constexpr (PW == 8) {  // level counts and level-2 prices (w6/w7 = price2 | count << 20)
-        i32 b2 = 0, a2 = 0;
-        i32 nb = hb ? b_levels(1, bb, depth, b2) : 0, na = ha ? b_levels(0, aa, depth, a2) : 0;
-        if ((u32)b2 >= (1u << 20) || (u32)a2 >= (1u << 20)) fail(ERR_RP_PRICE);
-        r.w[6] = (u32)b2 | ((u32)nb << 20);
-        r.w[7] = (u32)a2 | ((u32)na << 20);
-      }
-      ex_notify(sender, r);
+    case MK_SPREAD_REQ:
+      ex_notify(sender, ex_spread_reply((i32)m.w[1], closed));
       break;
-    }
     case MK_TV_REQ: {
       int perr = 0;
       i64 vol = transacted_volume(m_i64(m, 1), &perr);
@@ -2391,11 +2409,7 @@ struct Eng {
         fail(ERR_PANDAS_NO_TX);
         return;
       }
-      Msg r = msg_make(MK_TV, 0);
-      r.w[0] |= (1u << 11) | ((u32)closed << 7);
-      r.w[1] = (u32)(u64)vol;
-      r.w[2] = (u32)((u64)vol >> 32);
-      ex_notify(sender, r);
+      ex_notify(sender, ex_tv_reply(vol, closed));
       break;
     }
     case MK_STREAM_REQ: {  // QUERY_ORDER_STREAM (ExchangeAgent.py:251-279): history[1 : length + 1]
@@ -2848,11 +2862,18 @@ struct Eng {
 
   // ---------------- ValueAgent (ValueAgent.py:100-268)
   DEV void value_wakeup() {
+    if (!value_wake_head()) return;
+    cancel_all();
+    get_spread(1);
+    rs(AF_STATE, AS_AWAITING_SPREAD);
+  }
+  // wakeup up to its cancelOrders() / getCurrentSpread(); false: the wakeup ended before them
+  DEV bool value_wake_head() {
     ta_wakeup();
     rs(AF_STATE, AS_INACTIVE);
-    if (!fl(FL_HAS_OPEN) || !fl(FL_HAS_CLOSE)) return;
+    if (!fl(FL_HAS_OPEN) || !fl(FL_HAS_CLOSE)) return false;
     fl_set(FL_TRADING, true);
-    if (fl(FL_MKT_CLOSED) && fl(FL_DAILY_CLOSE)) return;
+    if (fl(FL_MKT_CLOSED) && fl(FL_DAILY_CLOSE)) return false;
     RS A = agent_rs();
     double dt = rs_exponential(A, 1.0 / PC.v_lambda);
     agent_rs_put(A);
@@ -2860,11 +2881,9 @@ struct Eng {
     if (fl(FL_MKT_CLOSED) && !fl(FL_DAILY_CLOSE)) {
       get_spread(1);
       rs(AF_STATE, AS_AWAITING_SPREAD);
-      return;
+      return false;
     }
-    cancel_all();
-    get_spread(1);
-    rs(AF_STATE, AS_AWAITING_SPREAD);
+    return true;
   }
   DEV void value_place() {
     i64 obs = o_observe(cur, v_sigma_n());
@@ -2945,15 +2964,21 @@ struct Eng {
     }
   }
   DEV void mm_receive(const Msg& m) {
+    i64 mid;
+    if (mm_note(m, mid)) mm_requote(mid);
+  }
+  // receiveMessage up to the both-replies-in test: TradingAgent.receiveMessage, then the order size
+  // from a QUERY_TRANSACTED_VOLUME reply or the mid from a QUERY_SPREAD reply.  false: the env failed
+  DEV bool mm_note(const Msg& m, i64& mid) {
     ta_receive(m, AG_POVMM);
-    i64 mid = rg64(AF_LAST_MID);
+    mid = rg64(AF_LAST_MID);
     u32 k = m_kind(m);
     if (k == MK_TV && fl(FL_AW_TV)) {
       i64 qty = py_round(mm_pov() * (double)rg64(AF_TV));
       const i64 mn = mm_min();
       if (qty > INT32_MAX) {  // the order words are 32-bit: stop loudly, never wrap
         fail(ERR_ORDER_SIZE);
-        return;
+        return false;
       }
       rs(AF_ORDER_SIZE, (u32)(qty >= mn ? qty : mn));
       fl_set(FL_AW_TV, false);
@@ -2968,6 +2993,10 @@ struct Eng {
         fl_set(FL_AW_SPREAD, false);
       }
     }
+    return true;
+  }
+  // with both replies in: cancel every open order, place the ladder around the mid, sleep a period
+  DEV void mm_requote(i64 mid) {
     if (!fl(FL_AW_SPREAD) && !fl(FL_AW_TV)) {
       cancel_all();
       const i64 ticks = mm_ticks();
@@ -5028,6 +5057,133 @@ struct Eng {
     atime_store(rcp, t);
     return n;
   }
+  // ---------------- exchange queries answered in place (zero-delay configurations)
+  // POVMarketMakerAgent.wakeup sends QUERY_SPREAD and QUERY_TRANSACTED_VOLUME at its own time t; with
+  // every delay 0 they are delivered at t and answered at t.  If no other pending event has time
+  // <= t, the next four pops of Kernel.runner are forced: the two requests at the exchange (key
+  // (t, 0), seqs s, s + 1: the smallest key there is), which push only the two replies (key
+  // (t, mm), seqs s + 2, s + 3) and read the book and the header without changing them; then the
+  // two replies at the market maker, the first of which pushes nothing while the agent still
+  // waits for the volume (FL_AW_TV).  So the wakeup's pop does all five here, in that order, with
+  // the market maker's record in registers throughout and no queue trip: the replies are built
+  // from the book in this wave's VGPRs and consumed at once.  Every observable is what the
+  // queued sequence leaves: pops, seq, the queue's high-water mark (two more than now, twice), the
+  // exchange's agentCurrentTimes, and in the instrumented kernels each elided pop's class counter,
+  // parity record and hash in pop order and the two record round trips of the replies.  Anything
+  // else (another event at t, stopTime or the close behind t, a launch budget that cuts the
+  // group, a queue without two free slots, a market maker that waits for the spread alone, a
+  // volume query that would raise) takes the queued path unchanged.
+  static constexpr bool SYNCQ_BASE = !BUILD && RUNS && !BLOG && !MD && !RP && !TIER && PC.ex_pipeline == 0;
+  static constexpr bool SYNCQ = SYNCQ_BASE && ((((MXA_SYNC_QUERY_MASK)) >> CFG) & 1) && PC.n_mm > 0;
+  // POVMarketMakerAgent.wakeup (mm_wakeup) with the group in place; returns the pops it handled
+  // beyond the wakeup's own (0: the queries were sent).  budget: pops this launch may still make,
+  // the wakeup's included
+  DEV int mm_cycle(i64 t, i64 budget) {
+    if (!ta_wakeup()) return 0;
+    const i64 lookback = mm_wake();  // lookback_period = wake_up_freq
+    int perr = 0;
+    i64 vol = 0;
+    bool ok = cur_agent < ACK_LIMIT && t <= PC.mkt_close && t <= stop_t && budget >= 5 && fl(FL_AW_TV) &&
+              qcount + 2 <= QCAP && bal((mk >> KSH) <= (u64)t) == 0;
+    if (ok) {
+      vol = transacted_volume(lookback, &perr);
+      ok = perr == 0;  // pandas would raise: the queued QUERY_TRANSACTED_VOLUME fails the env at its own pop
+    }
+    if (!ok) {
+      get_spread(1);
+      get_tv(lookback);
+      return 0;
+    }
+    PROF_CNT(76);  // in-place market-maker cycles (of the MM.wake calls)
+    const u64 kex = ((u64)t << KSH) | MT_MESSAGE, kmm = kex | ((u64)cur_agent << 2);
+    if (INSTR && (hash_on || trace)) {  // the two requests as send_ex queued them
+      Msg q = msg_make(MK_SPREAD_REQ, cur_agent);
+      q.w[1] = 1u;
+      account_pop(t, kex, q);
+      q = msg_make(MK_TV_REQ, cur_agent);
+      q.w[1] = (u32)(u64)lookback;
+      q.w[2] = (u32)((u64)lookback >> 32);
+      account_pop(t, kex, q);
+      if (lane == 0) h.kc[MXA_KC_REC] += 2;  // the replies' rec_load of the market maker
+    } else {
+      pops += 2;
+    }
+    seq += 4;
+    if constexpr (MAXQ_REG) maxq = qcount + 2 > maxq ? qcount + 2 : maxq;
+    else if (qcount + 2 > h.max_q) h.max_q = qcount + 2;
+    atime_store(0, t);
+    i64 mid;
+    const Msg rs_ = ex_spread_reply(1, false);
+    account_pop(t, kmm, rs_);
+    mm_note(rs_, mid);  // (cannot fail on a spread reply)
+    const Msg rv = ex_tv_reply(vol, false);
+    account_pop(t, kmm, rv);
+    if (mm_note(rv, mid)) mm_requote(mid);
+    return 4;
+  }
+
+  // ValueAgent.wakeup (value_wakeup) likewise: cancelOrders() sends a CANCEL_ORDER for its open
+  // order (a value agent holds at most one: every wake cancels, then places one) and
+  // getCurrentSpread() a QUERY_SPREAD, all to the exchange at t.  With no other event at <= t (the
+  // agent's own next wakeup, just set, included) the forced pops are: the CANCEL_ORDER and the
+  // QUERY_SPREAD at the exchange, then ORDER_CANCELLED (if the order still rested: del orders[id],
+  // the fast path of the event loop) and the spread reply at the agent, whose handler places the
+  // new order.  That LIMIT_ORDER is sent as an event: it can cross and fan out executions.
+  // More than one open order, or a list longer than one 64-entry chunk, takes the queued path.
+  static constexpr bool SYNCV = SYNCQ_BASE && ((((MXA_SYNC_VALUE_MASK)) >> CFG) & 1) && PC.n_value > 0;
+  DEV int value_cycle(i64 t, i64 budget) {
+    if (!value_wake_head()) return 0;
+    const i32 u = rgi(AF_NUSED), k = rgi(AF_NORD);
+    OpenOrder o;
+    o.oid = -1;
+    o.is_buy = o.qty = o.price = 0;
+    if (lane < u && u <= 64) o = open_ptr(cur_agent)[lane];
+    const u64 live = bal(o.oid != -1);
+    const bool ok = status == ST_RUNNING && cur_agent < ACK_LIMIT && t <= PC.mkt_close && t <= stop_t && k <= 1 && u <= 64 &&
+                    __popcll(live) == k && budget >= 3 + 2 * k && qcount + k + 1 <= QCAP && bal((mk >> KSH) <= (u64)t) == 0;
+    if (!ok) {
+      cancel_all();
+      get_spread(1);
+      rs(AF_STATE, AS_AWAITING_SPREAD);
+      return 0;
+    }
+    PROF_CNT(108);  // in-place value-agent wakes (of the VALUE.wake calls)
+    const u64 kex = ((u64)t << KSH) | MT_MESSAGE, kag = kex | ((u64)cur_agent << 2);
+    const bool instr = INSTR && (hash_on || trace);
+    bool found = false;
+    Msg cr;
+    int idx = 0;
+    if (k) {  // the CANCEL_ORDER at the exchange
+      idx = ctz64(live);
+      const Msg cm = msg_order(MK_CANCEL, rdli(o.oid, idx), cur_agent, rdli(o.is_buy, idx), rdli(o.qty, idx), rdli(o.price, idx), 0);
+      account_pop(t, kex, cm);
+      found = cancel_book(cm, cr);
+    }
+    if (instr) {  // the QUERY_SPREAD as send_ex queued it
+      Msg q = msg_make(MK_SPREAD_REQ, cur_agent);
+      q.w[1] = 1u;
+      account_pop(t, kex, q);
+    } else {
+      pops++;
+    }
+    atime_store(0, t);
+    const int np = k + 2 + (found ? 1 : 0);
+    seq += (u32)np;
+    if constexpr (MAXQ_REG) maxq = qcount + k + 1 > maxq ? qcount + k + 1 : maxq;
+    else if (qcount + k + 1 > h.max_q) h.max_q = qcount + k + 1;
+    if (found) {  // ORDER_CANCELLED at the agent: del self.orders[id]
+      account_pop(t, kag, cr);
+      del_open(idx);
+    }
+    const Msg r = ex_spread_reply(1, false);
+    account_pop(t, kag, r);
+    if (instr && lane == 0) h.kc[MXA_KC_REC] += found ? 2 : 1;  // the replies' record round trips
+    rs(AF_STATE, AS_AWAITING_SPREAD);
+    if (dirty) rng_maint();  // the wakeup's own event boundary, before the reply's draws
+    value_receive(r);
+    return np;
+  }
+
   DEV void run(i64 max_pops) {
     if constexpr (BLOG && EXT) {  // f_log's opening entry (kept by the build in o_pt / o_pv)
       if (pops == 0 && h.blog_n == 0 && h.o_pt >= 0) efo_log(h.o_pt, h.o_pv);
@@ -5226,7 +5382,10 @@ struct Eng {
         pc = pb + 32;
       }
 #endif
-      dispatch(rgi(AF_TYPE), type == MT_WAKEUP, m);
+      // a market maker's or a value agent's wakeup may take its exchange queries' pops with it
+      if (SYNCQ && type == MT_WAKEUP && rgi(AF_TYPE) == AG_POVMM) n += mm_cycle(t, max_pops - n);
+      else if (SYNCV && type == MT_WAKEUP && rgi(AF_TYPE) == AG_VALUE) n += value_cycle(t, max_pops - n);
+      else dispatch(rgi(AF_TYPE), type == MT_WAKEUP, m);
       PROF_ADD(pb, t0);
       PROF_CNT(pc);
       if (dirty) rng_maint();
