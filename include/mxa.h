@@ -239,7 +239,8 @@ int mxa_read_agents(mxa_handle* h, int32_t env, mxa_agent_state* out, int32_t ca
  * min(total, cap) are written (cap 0 / out4 NULL: count only). */
 int mxa_read_book(mxa_handle* h, int32_t env, int32_t side, int64_t* out4, int32_t cap);
 int mxa_read_trace(mxa_handle* h, int32_t env, int64_t* out /* [cap][10] */, int64_t cap, int64_t* n);
-/* replace the per-env seeds used by the next mxa_reset (n_envs values) */
+/* replace the per-env seeds used by the next mxa_reset (n_envs values).  An env that the next
+ * mxa_reset leaves alone (env_mask 0) keeps the episode and the seed it was built from. */
 int mxa_set_seeds(mxa_handle* h, const uint32_t* seeds);
 /* write the per-env episode record [n_envs][4] int64 = (events, hash, status, current_time)
  * into DEVICE memory on the handle's stream (e.g. a torch tensor to all-gather over RCCL) */
@@ -251,7 +252,9 @@ int mxa_write_results(mxa_handle* h, void* device_out);
  * 1.. of TradingAgent.holdings['CASH'], the share position and markToMarket - starting_cash
  * (TradingAgent.py:609-633; Kernel.py:330-341 averages the gain per agent type) for Kernel.runner
  * handles, the execution agent's own for GymKernel handles; word 11 is the caller's (a learner's
- * episode return).  Asynchronous on the handle's stream. */
+ * episode return).  seed is the one the env's episode was built from, i.e. the env's seed at the
+ * last mxa_reset that rebuilt it; a later mxa_set_seeds shows only once a reset has rebuilt the
+ * env.  Asynchronous on the handle's stream. */
 #define MXA_RECORD_WORDS 12
 int mxa_write_records(mxa_handle* h, void* device_out);
 /* event-class counters since the envs' last reset, kept by instrumented runs only (parity hash on

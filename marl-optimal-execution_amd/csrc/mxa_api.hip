@@ -74,6 +74,13 @@ __global__ void mxa_set_stop_kernel(char* base, uint64_t stride, int n, int64_t 
   if (i < n) ((EnvHdr*)(base + (size_t)i * stride))->t_stop = t_stop;
 }
 
+// the seeds of the episodes in progress (mxa_handle::d_built): a rebuilt env's (mask NULL: every
+// env's) becomes the current one of mxa_set_seeds, the others keep the seed they were built from
+__global__ void mxa_built_seeds_kernel(uint32_t* built, const uint32_t* seeds, const uint8_t* mask, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && (!mask || mask[i])) built[i] = seeds[i];
+}
+
 __global__ void mxa_results_kernel(const char* base, uint64_t stride, int n, int64_t* out) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -189,7 +196,8 @@ struct mxa_handle {
   int device = 0;
   hipStream_t own = nullptr, stream = nullptr;
   char* d_env = nullptr;
-  uint32_t* d_seeds = nullptr;
+  uint32_t* d_seeds = nullptr;  // the seeds the next mxa_reset builds from (mxa_set_seeds)
+  uint32_t* d_built = nullptr;  // the seed each env's current episode was built from (record word 5)
   uint8_t* d_mask = nullptr;
   int* d_count = nullptr;
   int32_t* d_list = nullptr;  // [n_envs] the running envs after a launch (mxa_compact_kernel)
@@ -664,6 +672,7 @@ static int create_common(mxa_handle* h, int32_t n_envs, const uint32_t* seeds, i
   size_t bytes = (size_t)h->P.L.env_stride * n_envs;
   HIPCHK(h, hipMalloc(&h->d_env, bytes));
   HIPCHK(h, hipMalloc(&h->d_seeds, sizeof(uint32_t) * n_envs));
+  HIPCHK(h, hipMalloc(&h->d_built, sizeof(uint32_t) * n_envs));
   HIPCHK(h, hipMalloc(&h->d_mask, n_envs));
   HIPCHK(h, hipMalloc(&h->d_count, sizeof(int)));
   HIPCHK(h, hipMalloc(&h->d_list, sizeof(int32_t) * (size_t)std::max(1, h->P.n_envs)));
@@ -921,6 +930,9 @@ int mxa_reset(mxa_handle* h, const uint8_t* mask) {
   }
   h->build(dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, h->P.n_envs, h->d_seeds, dm,
            h->d_ctx);
+  HIPCHK(h, hipGetLastError());
+  hipLaunchKernelGGL(mxa_built_seeds_kernel, dim3((h->P.n_envs + 255) / 256), dim3(256), 0, h->stream, h->d_built,
+                     h->d_seeds, dm, h->P.n_envs);
   HIPCHK(h, hipGetLastError());
   if (!mask) h->started = false;
   if (h->exlog) {  // the build cleared the header: the switch outlives resets
@@ -1261,7 +1273,7 @@ int mxa_write_records(mxa_handle* h, void* device_out) {
   int n = h->P.n_envs;
   // GymKernel handles: the execution agent; Kernel.runner handles: every trading agent
   const int a0 = h->gym ? h->P.first_rl : 1, a1 = h->gym ? h->P.first_rl + 1 : h->P.n_agents;
-  hipLaunchKernelGGL(mxa_records_kernel, dim3(n), dim3(64), 0, h->stream, h->d_env, h->P.L.env_stride, n, h->d_seeds,
+  hipLaunchKernelGGL(mxa_records_kernel, dim3(n), dim3(64), 0, h->stream, h->d_env, h->P.L.env_stride, n, h->d_built,
                      h->P.L.off_ag, a0, a1, (int64_t*)device_out);
   HIPCHK(h, hipGetLastError());
   return MXA_OK;
@@ -1333,6 +1345,7 @@ void mxa_destroy(mxa_handle* h) {
   hipSetDevice(h->device);
   if (h->d_env) hipFree(h->d_env);
   if (h->d_seeds) hipFree(h->d_seeds);
+  if (h->d_built) hipFree(h->d_built);
   if (h->d_mask) hipFree(h->d_mask);
   if (h->d_count) hipFree(h->d_count);
   if (h->d_list) hipFree(h->d_list);

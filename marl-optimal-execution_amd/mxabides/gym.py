@@ -56,17 +56,27 @@ class VecABIDESEnv:
             raise _lib.MxaError("%s failed (%d): %s" % (what, rc, msg))
         return rc
 
-    def reset(self, seeds=None):
-        """ABIDESEnv.reset for every env (ABIDESEnv.py:51-57).  Each env is one process running
-        consecutive episodes: Order.order_id / Order._order_ids carry over from its previous
-        episode (util/order/Order.py:8-9) unless
-        set_id_persistence(False) made every reset a fresh process."""
-        if seeds is not None:  # rmsc03 + DummyRL: new per-env seeds
+    def reset(self, seeds=None, mask=None):
+        """ABIDESEnv.reset for every env (ABIDESEnv.py:51-57), or with `mask` ([n_envs], nonzero =
+        reset) for the masked envs only: the others keep their episode, their seed and their
+        `obs` / `flags` rows.  Each env is one process running consecutive episodes:
+        Order.order_id / Order._order_ids carry over from its previous episode
+        (util/order/Order.py:8-9) unless set_id_persistence(False) made
+        every reset a fresh process."""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+            if len(m) != self.n_envs:
+                raise ValueError("mask: one entry per env")
+        if seeds is not None:  # rmsc03 + DummyRL: new per-env seeds (a full list; unmasked entries wait)
             sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+            if len(sd) != self.n_envs:
+                raise ValueError("seeds: one per env")
             self._check(self.L.mxa_set_seeds(self._h, sd.ctypes.data), "mxa_set_seeds")
-        self._check(self.L.mxa_reset(self._h, None), "mxa_reset")
-        self.obs[:] = 0
-        self.flags[:] = 0
+        self._check(self.L.mxa_reset(self._h, m.ctypes.data if m is not None else None), "mxa_reset")
+        rows = slice(None) if m is None else m != 0
+        self.obs[rows] = 0
+        self.flags[rows] = 0
 
     def set_id_persistence(self, on):
         """True (default): resets continue each env's order ids (one process); False: every

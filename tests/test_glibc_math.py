@@ -2,27 +2,16 @@
 compiled for the host must agree bit for bit with the host libm (the libm the
 reference's math/numpy calls resolve to) on the argument distributions of the path."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "glibc_math_host.cpp")
-LIB = os.path.join(ROOT, "tests", "native", "build", "libgm_host.so")
+import glibc_math_cases as cases
 
 
 @pytest.fixture(scope="module")
 def gm():
-    os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-ffp-contract=off", "-fno-builtin",
-                           "-I" + os.path.join(ROOT, "marl-optimal-execution_amd", "csrc"), SRC, "-o", LIB, "-lm"])
-    L = ctypes.CDLL(LIB)
-    L.gm_check.restype = ctypes.c_int64
-    L.gm_check.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                           ctypes.POINTER(ctypes.c_int64)]
-    return L
+    return cases.host_lib()
 
 
 def _check(L, mode, x, y=None):
@@ -30,7 +19,7 @@ def _check(L, mode, x, y=None):
     y = np.ascontiguousarray(x if y is None else y, dtype=np.float64)
     first = ctypes.c_int64()
     bad = L.gm_check(mode, x.ctypes.data, y.ctypes.data, len(x), ctypes.byref(first))
-    assert bad == 0, "first mismatch at x=%r y=%r" % (x[first.value], y[first.value])
+    assert bad == 0, "%d mismatches, first at x=%r y=%r" % (bad, x[first.value], y[first.value])
 
 
 N = 400_000
@@ -63,3 +52,29 @@ def test_pow(gm):
     _check(gm, 2, rs.uniform(0, 10, N), rs.uniform(-50, 50, N))
     _check(gm, 2, -rs.uniform(0, 10, N), np.floor(rs.uniform(-50, 50, N)))
     _check(gm, 2, rs.uniform(0, 3, N), rs.uniform(-3000, 3000, N))
+
+
+def test_path_families_are_the_shared_ones(gm):
+    """the device test (tests/test_gpu_parity.py) runs cases.path_families: the same 15 families
+    as test_log / test_exp / test_pow above, here at its size"""
+    fam = cases.path_families(200_000)
+    assert len(fam) == 15
+    for name, mode, x, y in fam:
+        _check(gm, mode, x, y)
+
+
+def test_edge_families(gm):
+    """the branches a runtime composition can move the arguments into (cases.edge_families): exp's
+    overflow and underflow windows, pow with a negative base, a subnormal base, tiny and huge y, a
+    base next to 1, the square root, and both ends of log's near-1 window"""
+    for name, mode, x, y in cases.edge_families(200_000):
+        _check(gm, mode, x, y)
+
+
+def test_special_values(gm):
+    """zeros, infinities, NaN, subnormals and the thresholds through log and exp, and every pair of
+    them through pow"""
+    fam = cases.special_families()
+    assert len(fam[2][2]) == len(cases.special_values()) ** 2 >= 1444
+    for name, mode, x, y in fam:
+        _check(gm, mode, x, y)

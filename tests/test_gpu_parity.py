@@ -69,6 +69,77 @@ def test_device_glibc_math(mx):
         assert (out[idx].view(np.uint64) == ref.view(np.uint64)).all()
 
 
+@pytest.fixture(scope="module")
+def gm():
+    """the host build of csrc/glibc_math.h (pinned to libm by tests/test_glibc_math.py on these
+    very families): gm_eval is the reference of the device compile"""
+    import glibc_math_cases as cases
+    return cases.host_lib()
+
+
+def _device_math(L, mode, x, y=None):
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(x if y is None else y, dtype=np.float64)
+    out = np.zeros(len(x))
+    assert L.mxa_math_probe(0, mode, x.ctypes.data, y.ctypes.data, out.ctypes.data, len(x)) == 0
+    return out
+
+
+def _assert_device_equals_host(L, gm, fam):
+    import glibc_math_cases as cases
+    for name, mode, x, y in fam:
+        dev, ref = _device_math(L, mode, x, y), cases.host_eval(gm, mode, x, y)
+        bad = np.nonzero(~cases.same_bits(dev, ref))[0]
+        assert len(bad) == 0, "%s: %d of %d differ, first x=%r y=%r device %r host %r" % (
+            name, len(bad), len(x), x[bad[0]], None if y is None else y[bad[0]], dev[bad[0]], ref[bad[0]])
+
+
+def test_device_glibc_math_whole_arrays(mx, gm):
+    """the device compile of csrc/glibc_math.h against its host build, every value bit for bit
+    (two NaNs equal): the 15 families of tests/test_glibc_math.py and the edge families (exp's
+    overflow and underflow windows, pow with a negative base, a subnormal base, tiny and huge y, a
+    base next to 1, the execution agent's square root, both ends of log's near-1 window)"""
+    import glibc_math_cases as cases
+    fam = cases.path_families(200_000) + cases.edge_families(200_000)
+    assert len(fam) == 25 and all(len(x) == 200_000 for _, _, x, _ in fam)
+    _assert_device_equals_host(mx.load(), gm, fam)
+
+
+def test_device_glibc_math_special_values(mx, gm):
+    """zeros, infinities, NaN, subnormals, the integers around 2^53 and exp's thresholds through
+    log and exp, and every pair of them through pow"""
+    import glibc_math_cases as cases
+    _assert_device_equals_host(mx.load(), gm, cases.special_families())
+
+
+RNG_CASES = [(2, "randint", (0, 2 ** 32)),       # rng == 0xFFFFFFFF: the draw of every agent seed
+             (2, "randint", (0, 64)),            # a power of two: the mask equals the range
+             (2, "randint", (0, 65)),            # just above one: about half the draws are rejected
+             (2, "randint", (-50, 50)), (2, "randint", (0, 2 ** 31 + 1)),
+             (2, "randint", (1, 3)), (2, "randint", (5, 6)),   # one-bit mask; a single value draws nothing
+             (3, "normal", (0.0, 1.0)), (3, "normal", (1e5, 1000 ** 0.5)), (3, "normal", (-3.5, 1e-9)),
+             (4, "exponential", (1e12,)), (4, "exponential", (1.0,)), (4, "exponential", (5.7e-12,)),
+             (5, "uniform", (21000.0, 1.3e7)), (5, "uniform", (-1.0, 1.0))]
+
+
+@pytest.mark.parametrize("seed", [0, 424242, 4294967295])
+def test_device_rng_matches_numpy(mx, seed):
+    """mxa_rng_probe against numpy.random.RandomState itself, one draw at a time, float64 bit
+    patterns: randint at its three branches and their edges, the distributions at the scales a
+    composition's parameters give them"""
+    L = mx.load()
+    n = 3000
+    for mode, fn, args in RNG_CASES:
+        out = np.zeros(n, dtype=np.float64)
+        a, b = (float(args[0]), float(args[1]) if len(args) > 1 else 0.0)
+        assert L.mxa_rng_probe(0, seed, mode, a, b, n, out.ctypes.data) == 0
+        r = np.random.RandomState(seed)
+        draw = getattr(r, fn)
+        ref = np.array([float(draw(*args)) for _ in range(n)], dtype=np.float64)
+        bad = np.nonzero(out.view(np.uint64) != ref.view(np.uint64))[0]
+        assert len(bad) == 0, (fn, args, int(bad[0]), out[bad[0]], ref[bad[0]])
+
+
 @pytest.mark.parametrize("cfg,seed", FIXTURES)
 def test_gpu_trace_matches_reference(mx, cfg, seed):
     d, ref = load(cfg, seed)
