@@ -1479,7 +1479,10 @@ struct Eng {
     // on the chain; placement is invisible to the pop: replay step 0.361 -> 0.356 ms, rmsc03 41.5
     // -> 40.8, sparse_zi_1000 725 -> 721, same per-env digests), then its first free slot
     const int L = ctz64(b);
-    const int jl = qm_ctz(qm_rdl(use, L));  // lane L has a free slot
+    q_push_at(L, qm_ctz(qm_rdl(use, L)), key, seq, m);  // lane L has a free slot
+  }
+  // the event into free slot jl of lane L
+  DEV void q_push_at(int L, int jl, u64 key, u32 seq, const Msg& m) {
     const bool me = lane == L;
     qset(jl, key, seq, me);
     // lane L's minimum and free mask by selects, not a branch: the short-circuit test inside a
@@ -4834,44 +4837,53 @@ struct Eng {
   // the run.  Ids are unique among live orders, so at most one live slot matches a member;
   // members that share a bucket (ids 64 apart, or one id cancelled twice) take the serial path,
   // which finds the orders member by member exactly as the reference's sequence does.
-  DEV void run_ex_cancel(i64 t, const Msg& mm, int n) {
-    i32 nq = 0, nm = 0;
-    bool found = false;
-    const bool mem = lane < n;
-    const i32 moid = (i32)mm.w[1], mprice = (i32)mm.w[3];
-    const i32 mside = m_buy(mm);
+  // the bucket pass: hit[j] = the member (lane) that cancels book slot (j, lane), or -1.  Reads
+  // the book only; false: two members share a bucket (hit is not set)
+  DEV bool ex_cancel_find(bool mem, i32 moid, i32 mprice, i32 mside, int (&hit)[SO]) {
     scr[lane] = -1;
     __threadfence_block();
     if (mem) scr[moid & 63] = lane;
     __threadfence_block();
     const bool coll = mem && scr[moid & 63] != lane;
-    if (!bal(coll)) {
-      int hit[SO];
-      int nfreed = 0;
-      for (int j = 0; j < SO; j++) {
-        const int c = scr[bo[j] & 63];
-        const int cs = c < 0 ? 0 : c;
-        const i32 co = __shfl(moid, cs, 64), cp = __shfl(mprice, cs, 64), csd = __shfl(mside, cs, 64);
-        hit[j] = (bm[j] >= 0 && c >= 0 && bo[j] == co && bp[j] == cp && (bm[j] & 1) == csd) ? c : -1;
-      }
-      __threadfence_block();
-      scr[lane] = -1;
-      __threadfence_block();
-      for (int j = 0; j < SO; j++) {
-        if (hit[j] >= 0) scr[hit[j]] = j * 64 + lane;  // member -> its book slot
-        nfreed += __popcll(bal(hit[j] >= 0));
-      }
-      __threadfence_block();
-      const int s = scr[lane];
-      const int sl = s < 0 ? 0 : (s & 63), sj = s < 0 ? 0 : (s >> 6);
-      for (int j = 0; j < SO; j++) {
-        const i32 q = __shfl(bq[j], sl, 64), mt = __shfl(bm[j], sl, 64);
-        nq = sj == j ? q : nq;
-        nm = sj == j ? mt : nm;
-      }
-      found = s >= 0;
-      for (int j = 0; j < SO; j++) bm[j] = hit[j] >= 0 ? -1 : bm[j];  // b_free
-      h.b_count -= nfreed;
+    if (bal(coll)) return false;
+    for (int j = 0; j < SO; j++) {
+      const int c = scr[bo[j] & 63];
+      const int cs = c < 0 ? 0 : c;
+      const i32 co = __shfl(moid, cs, 64), cp = __shfl(mprice, cs, 64), csd = __shfl(mside, cs, 64);
+      hit[j] = (bm[j] >= 0 && c >= 0 && bo[j] == co && bp[j] == cp && (bm[j] & 1) == csd) ? c : -1;
+    }
+    return true;
+  }
+  // the orders ex_cancel_find matched leave the book; member i (lane i) learns whether its order
+  // rested, and the book's quantity and (owner << 1 | side) of it
+  DEV void ex_cancel_take(const int (&hit)[SO], bool& found, i32& nq, i32& nm) {
+    int nfreed = 0;
+    __threadfence_block();
+    scr[lane] = -1;
+    __threadfence_block();
+    for (int j = 0; j < SO; j++) {
+      if (hit[j] >= 0) scr[hit[j]] = j * 64 + lane;  // member -> its book slot
+      nfreed += __popcll(bal(hit[j] >= 0));
+    }
+    __threadfence_block();
+    const int s = scr[lane];
+    const int sl = s < 0 ? 0 : (s & 63), sj = s < 0 ? 0 : (s >> 6);
+    for (int j = 0; j < SO; j++) {
+      const i32 q = __shfl(bq[j], sl, 64), mt = __shfl(bm[j], sl, 64);
+      nq = sj == j ? q : nq;
+      nm = sj == j ? mt : nm;
+    }
+    found = s >= 0;
+    for (int j = 0; j < SO; j++) bm[j] = hit[j] >= 0 ? -1 : bm[j];  // b_free
+    h.b_count -= nfreed;
+  }
+  DEV void run_ex_cancel(i64 t, const Msg& mm, int n) {
+    i32 nq = 0, nm = 0;
+    bool found = false;
+    const bool mem = lane < n;
+    int hit[SO];
+    if (ex_cancel_find(mem, (i32)mm.w[1], (i32)mm.w[3], m_buy(mm), hit)) {
+      ex_cancel_take(hit, found, nq, nm);
     } else {
       for (int i = 0; i < n; i++) {
         const u32 w0 = rdl(mm.w[0], i);
@@ -4908,17 +4920,14 @@ struct Eng {
     for (int j = 0; j < SO; j++) nfree += __popcll(bal(bm[j] < 0));
     return maxb < ba && mins > bb && maxb < mins && nfree >= m;
   }
-  DEV void run_ex_limit(i64 t, const Msg& mm, int n) {
-    const bool v = lane < n && (i32)mm.w[2] > 0;
-    const int buy = m_buy(mm);
-    const i32 price = (i32)mm.w[3];
+  // the valid members (v) enter the book in lane order; returns how many
+  DEV int ex_limit_book(bool v, int buy, i32 price, i32 oid, i32 agent, i32 qty) {
     const u64 vb = bal(v);
     const int m = __popcll(vb);
     if (m > 0) {
       const int r = (int)__builtin_amdgcn_mbcnt_hi((u32)(vb >> 32), __builtin_amdgcn_mbcnt_lo((u32)vb, 0u));
       if (v) scr[r] = lane;  // rank -> member lane
       __threadfence_block();
-      const i32 agent = m_agent(mm), qty = (i32)mm.w[2], oid = (i32)mm.w[1];
       const i32 meta = (agent << 1) | buy;
       const i32 hep = h.epoch;
       const u32 arr0 = h.arrival;
@@ -4960,6 +4969,15 @@ struct Eng {
       LDSP i32* EP = ep_entries();
       const i32 ne = EP[h.epoch & 15] + m;
       if (lane == 0) EP[h.epoch & 15] = ne;
+    }
+    return m;
+  }
+  DEV void run_ex_limit(i64 t, const Msg& mm, int n) {
+    const bool v = lane < n && (i32)mm.w[2] > 0;
+    const int buy = m_buy(mm);
+    const i32 price = (i32)mm.w[3];
+    const i32 agent = m_agent(mm), qty = (i32)mm.w[2], oid = (i32)mm.w[1];
+    if (ex_limit_book(v, buy, price, oid, agent, qty) > 0) {
       const Msg a = msg_order(MK_ACCEPTED, oid, agent, buy, qty, price, 0);
       const u64 akey = ((u64)(t + PC.ex_pipeline) << KSH) | ((u64)(u32)agent << 2) | MT_MESSAGE;
       q_push_lanes(v, akey, a);
@@ -4969,6 +4987,12 @@ struct Eng {
   // (the same id buckets as run_ex_cancel: each live list entry looks up its id; a shared
   // bucket takes the serial path)
   DEV void run_ta_cancelled(int rcp, i64 t, const Msg& mm, int n, OpenOrder* my) {
+    ta_cancelled_list(rcp, mm, n, my);
+    rs64(AF_ATIME, t);
+    rec_store();
+  }
+  // the list update of the run: the members' entries become tombstones (my: the list's chunks)
+  DEV void ta_cancelled_list(int rcp, const Msg& mm, int n, OpenOrder* my) {
     i32 u = rgi(AF_NUSED), nord = rgi(AF_NORD);
     u32 dead = 0;
     const i32 moid = (i32)mm.w[1];
@@ -5010,8 +5034,6 @@ struct Eng {
       if ((dead >> j) & 1) oo[j * 64 + lane].oid = -1;
     rs(AF_NORD, (u32)nord);
     rs(AF_NUSED, (u32)u);
-    rs64(AF_ATIME, t);
-    rec_store();
   }
   // one run starting at the popped event; returns the pops handled (0: pop it one by one)
   DEV int run_event(u64 key, u32 s0, i64 t, int rcp, u32 kind, i64 budget) {
@@ -5075,6 +5097,177 @@ struct Eng {
   // volume query that would raise) takes the queued path unchanged.
   static constexpr bool SYNCQ_BASE = !BUILD && RUNS && !BLOG && !MD && !RP && !TIER && PC.ex_pipeline == 0;
   static constexpr bool SYNCQ = SYNCQ_BASE && ((((MXA_SYNC_QUERY_MASK)) >> CFG) & 1) && PC.n_mm > 0;
+  // ---------------- the market maker's cancel and ladder runs in place
+  // At mm_requote inside mm_cycle nothing else is pending at <= t.  cancel_all's CANCEL_ORDERs and
+  // the ladder's LIMIT_ORDERs carry key (t, 0, MESSAGE), the smallest there is, and consecutive
+  // seqs: they pop next, cancels first, and their handlers push only replies at (t, mm, MESSAGE)
+  // with later seqs (no ladder order matches, so no third agent hears of it).  Those replies are
+  // then the only events at t and pop in seq order, ORDER_CANCELLED then ORDER_ACCEPTED, and
+  // neither handler pushes; the wakeup at t + mm_wake() sorts after them all.  So the same pop
+  // handles the four runs, member i in lane i, with the book code of the queued runs, and only
+  // the next wakeup is pushed: into the slot it takes after cancel_all's and the ladder's batched
+  // pushes (the free slot of rank nc + NL in q_push_lanes's lane-major order).  All or nothing,
+  // decided before the first effect; any failing test runs mm_requote as it is.  The observables
+  // are the queued sequence's: pops, seq (s .. s+nc-1 the cancels, NL ladder orders, the wakeup,
+  // nc ORDER_CANCELLED, NL ORDER_ACCEPTED), the queue's high-water mark qcount + nc + NL + 1, the
+  // open-order list (ladder appended, compacted where mm_place_ladder compacts, then the cancelled
+  // entries tombstoned), the book, and in the instrumented kernels every elided pop's accounting.
+  // The fall-backs, beyond mm_cycle's own: more than 64 live list entries; a first cancel that
+  // would be popped alone (the only live entry of its 64-entry list chunk: the queued path then
+  // counts no run for it); two cancels in one id bucket (run_ex_cancel's serial path); a cancel
+  // whose order no longer rests; a launch budget or a queue too small for the whole group; a
+  // ladder mm_requote would place order by order; a ladder order that could match or overflow the
+  // book as the cancels leave it.
+  static constexpr bool LADDER_RQ = MXA_LADDER_REPLIES_QUEUED != 0;
+  static constexpr int MM_CNL = 2 * ((int)PC.mm_ticks + 1);
+  static constexpr bool SYNCL = SYNCQ && ((((MXA_SYNC_LADDER_MASK)) >> CFG) & 1) && !PC.mm_rt && BATCH && !TIER && MM_CNL <= 64;
+  // mm_requote(mid) at the volume reply of mm_cycle; returns the pops handled in place (0: queued).
+  // budget: as mm_cycle's
+  DEV int mm_ladder_cycle(i64 t, i64 mid, i64 budget) {
+    constexpr int CNB = (int)PC.mm_ticks + 1, CNL = MM_CNL;
+    if (fl(FL_AW_SPREAD) || fl(FL_AW_TV)) return 0;  // (mm_requote: a reply is still out)
+    const i32 u = rgi(AF_NUSED), nord = rgi(AF_NORD);
+    const i64 sz = rgi(AF_ORDER_SIZE);
+    const i64 la = mid + PC.mm_window, lb = mid - 1 - PC.mm_ticks;
+    OpenOrder* oo = open_ptr(cur_agent);
+    // cancel_all's members: the live list entries in list order, member i to lane i
+    OpenOrder my[OC];
+    for (int j = 0; j < OC; j++) {
+      my[j].oid = -1;
+      my[j].is_buy = my[j].qty = my[j].price = 0;
+      if (j * 64 + lane < u) my[j] = oo[j * 64 + lane];
+    }
+    int nc = 0, first = 0;
+    for (int j = 0; j < OC; j++) {
+      const bool live = my[j].oid != -1;
+      const u64 b = bal(live);
+      const int r = nc + (int)__builtin_amdgcn_mbcnt_hi((u32)(b >> 32), __builtin_amdgcn_mbcnt_lo((u32)b, 0u));
+      if (live && r < 64) scr[r] = j * 64 + lane;
+      first = first ? first : __popcll(b);  // the batch cancel_all pushes first
+      nc += __popcll(b);
+    }
+    __threadfence_block();
+    const bool mem = lane < nc;
+    const int pos = mem ? scr[lane] : 0;  // (every scr[0..63] is written when nc > 64)
+    OpenOrder o;
+    o.oid = -1;
+    o.is_buy = o.qty = o.price = 0;
+    for (int j = 0; j < OC; j++) {
+      const i32 a = __shfl(my[j].oid, pos & 63, 64), b = __shfl(my[j].is_buy, pos & 63, 64),
+                c = __shfl(my[j].qty, pos & 63, 64), d = __shfl(my[j].price, pos & 63, 64);
+      const bool me = mem && (pos >> 6) == j;
+      o.oid = me ? a : o.oid;
+      o.is_buy = me ? b : o.is_buy;
+      o.qty = me ? c : o.qty;
+      o.price = me ? d : o.price;
+    }
+    bool ok = nc <= 64 && (nc == 0 || first >= 2) && sz > 0 && nord + CNL <= PC.L.open_cap && nc + CNL <= PC.L.open_cap &&
+              budget >= 5 + (LADDER_RQ ? 1 : 2) * (nc + CNL) && qcount + nc + CNL + 1 <= QCAP && lb >= 0 && la + PC.mm_ticks <= INT32_MAX;
+    int hit[SO];
+    if (ok) ok = ex_cancel_find(mem, o.oid, o.price, o.is_buy, hit);
+    if (ok) {
+      // run_ex_limit_ok on the book as the cancels leave it (the slots they do not hit; these are
+      // the other agents' orders, the market maker's own all being cancelled).  With rmsc03's
+      // constants the match test cannot fire (the mid was read from this book at t, the ladder
+      // stays a cent or more outside it); it is the queued path's guard, and the room test is needed
+      i32 bbo = INT32_MIN, bao = INT32_MAX;
+      int nfree = 0, nf = 0;
+      for (int j = 0; j < SO; j++) {
+        const bool stay = bm[j] >= 0 && hit[j] < 0, buy = (bm[j] & 1) != 0;
+        bbo = stay && buy && bp[j] > bbo ? bp[j] : bbo;
+        bao = stay && !buy && bp[j] < bao ? bp[j] : bao;
+        nfree += __popcll(bal(!stay));
+        nf += __popcll(bal(hit[j] >= 0));
+      }
+      bbo = wmax_i32(bbo);
+      bao = wmin_i32(bao);
+      const i32 maxb = (i32)(mid - 1), mins = (i32)la;
+      ok = nf == nc && maxb < bao && mins > bbo && maxb < mins && nfree >= CNL;
+    }
+    // the pending wakeup's slot: the free slot of rank nc + CNL, lanes first (q_push_lanes)
+    int wl = 0, wj = 0;
+    if (ok) {
+      const int R = nc + CNL, c = qm_pop(qfree);
+      int base = 0;
+      for (int k = 0; k < SQ; k++) {
+        const u64 b = bal(c > k);
+        base += (int)__builtin_amdgcn_mbcnt_hi((u32)(b >> 32), __builtin_amdgcn_mbcnt_lo((u32)b, 0u));
+      }
+      const u64 lb_ = bal(base <= R && R < base + c);
+      QM f = qfree;
+      for (int k = 0; k < SQ; k++)
+        if (k < R - base) f &= f - 1;
+      ok = lb_ != 0;  // (qcount + nc + CNL + 1 <= QCAP: there is such a slot)
+      wl = ok ? ctz64(lb_) : 0;
+      wj = (int)rdl((u32)(f ? qm_ctz(f) : 0), wl);
+    }
+    if (!ok) {
+      mm_requote(mid);
+      return 0;
+    }
+    PROF_CNT(111);  // in-place cancel / ladder groups (of the in-place cycles)
+    const u64 kex = ((u64)t << KSH) | MT_MESSAGE, kmm = kex | ((u64)cur_agent << 2);
+    // CANCEL_ORDER x nc at the exchange
+    bool found;
+    i32 nq = 0, nm = 0;
+    run_account(kex, t, msg_order(MK_CANCEL, o.oid, cur_agent, o.is_buy, o.qty, o.price, 0), nc);
+    ex_cancel_take(hit, found, nq, nm);
+    // LIMIT_ORDER x CNL at the exchange (mm_place_ladder's members)
+    const bool act = lane < CNL;
+    const int buy = lane < CNB;
+    const i32 price = (i32)(buy ? lb + lane : la + (lane - CNB));
+    const i32 oid = (i32)(ocnt + lane);
+    ocnt += CNL;
+    Msg lm = msg_order(MK_LIMIT, oid, cur_agent, buy, (i32)sz, price, 0);
+    run_account(kex, t, lm, CNL);
+    ex_limit_book(act, buy, price, oid, cur_agent, (i32)sz);
+    const Msg rc = msg_order(MK_CANCELLED, o.oid, nm >> 1, nm & 1, nq, o.price, 0);
+    lm.w[0] = (lm.w[0] & ~63u) | MK_ACCEPTED;
+    // the open-order list: the ladder appended (after mm_place_ladder's open_compact, which leaves
+    // the nc members, the only live entries, in [0, nc)), then the cancelled entries tombstoned
+    const bool cmp = u + CNL > PC.L.open_cap;
+    const i32 u2 = cmp ? nc : u;
+    if (mem) {
+      if (cmp) {
+        OpenOrder d = o;
+        if constexpr (!LADDER_RQ) d.oid = -1;
+        oo[lane] = d;
+      } else if constexpr (!LADDER_RQ) {
+        oo[pos].oid = -1;
+      }
+    }
+    if (act) {
+      OpenOrder d;
+      d.oid = oid;
+      d.is_buy = buy;
+      d.qty = (i32)sz;
+      d.price = price;
+      oo[u2 + lane] = d;
+    }
+    rs(AF_NUSED, (u32)(u2 + CNL));
+    // the queue: its peak, the seqs, the next wakeup
+    const int hw = qcount + nc + CNL + 1;
+    if constexpr (MAXQ_REG) maxq = hw > maxq ? hw : maxq;
+    else if (hw > h.max_q) h.max_q = hw;
+    const u32 s = seq;
+    fl_set(FL_AW_SPREAD, true);
+    fl_set(FL_AW_TV, true);
+    q_push_at(wl, wj, ((u64)(t + mm_wake()) << KSH) | ((u64)cur_agent << 2) | MT_WAKEUP, s + (u32)(nc + CNL), msg_make(MK_WAKEUP, 0));
+    if constexpr (LADDER_RQ) {  // the measured variant: the replies go through the queue as runs
+      rs(AF_NORD, (u32)(nord + CNL));
+      seq = s + (u32)(nc + CNL + 1);
+      q_push_lanes(mem, kmm, rc);
+      q_push_lanes(act, kmm, lm);
+      return nc + CNL;
+    }
+    // ORDER_CANCELLED x nc (the book's quantity and owner), ORDER_ACCEPTED x CNL at the market maker
+    run_account(kmm, t, rc, nc);
+    if (INSTR && (hash_on || trace) && lane == 0 && nc > 0) h.kc[MXA_KC_REC]++;  // the ORDER_CANCELLED run's rec_load
+    run_account(kmm, t, lm, CNL);
+    rs(AF_NORD, (u32)(nord + CNL - nc));  // (> 0: run_ta_cancelled's reset of an empty list cannot apply)
+    seq = s + (u32)(2 * nc + 2 * CNL + 1);
+    return 2 * nc + 2 * CNL;
+  }
   // POVMarketMakerAgent.wakeup (mm_wakeup) with the group in place; returns the pops it handled
   // beyond the wakeup's own (0: the queries were sent).  budget: pops this launch may still make,
   // the wakeup's included
@@ -5118,7 +5311,10 @@ struct Eng {
     mm_note(rs_, mid);  // (cannot fail on a spread reply)
     const Msg rv = ex_tv_reply(vol, false);
     account_pop(t, kmm, rv);
-    if (mm_note(rv, mid)) mm_requote(mid);
+    if (mm_note(rv, mid)) {
+      if constexpr (SYNCL) return 4 + mm_ladder_cycle(t, mid, budget);
+      else mm_requote(mid);
+    }
     return 4;
   }
 

@@ -51,6 +51,8 @@ for i, nm in enumerate(["ZI SPREAD (place)", "ZI ACCEPTED", "ZI EXECUTED", "ZI o
 # exchange queries answered in place (Eng::mm_cycle / value_cycle): groups taken, of the wakes (counts 25, 23)
 print("in-place groups      MM %d of %d wakes (%.1f%%), VALUE %d of %d wakes (%.1f%%)"
       % (v[76], v[25], 100.0 * v[76] / max(v[25], 1), v[108], v[23], 100.0 * v[108] / max(v[23], 1)))
+# ... and the market maker's cancel / ladder group with it (Eng::mm_ladder_cycle, count 111)
+print("in-place ladder      MM %d of %d wakes (%.1f%%)" % (v[111], v[25], 100.0 * v[111] / max(v[25], 1)))
 print("inclusive function timers (nested inside the phases above; cycles per call)")
 for slot, nm in [(64, "send"), (65, "q_push"), (66, "handle_limit"), (67, "cancel_order"), (68, "b_best"),
                  (69, "o_observe"), (70, "bayes_r_T"), (71, "cancel_all"), (72, "place_limit"), (73, "ex_receive"),
