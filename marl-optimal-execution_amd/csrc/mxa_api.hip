@@ -204,6 +204,7 @@ struct mxa_handle {
   int64_t first_chunk = 0;    // mxa_set_launch_schedule: mxa_run's first launch (0: every launch `chunk`)
   size_t lds = 0;
   mxa_build_fn build = nullptr;
+  mxa_inplace_fn inplace = nullptr;                // in-place group counts of the configuration (mxa_read_inplace)
   mxa_run_fn run = nullptr, run_log = nullptr;     // run_log: with the book-update log
   mxa_run_fn run_fast = nullptr;                   // hash off, no trace ring: instrumentation compiled out
   mxa_step_fn step = nullptr, step_fast = nullptr;  // GymKernel handles (replay, rmsc03_rl)
@@ -288,6 +289,7 @@ static bool bind(mxa_handle* h, int cfg) {
   default: return false;
   }
   h->build = e.build;
+  h->inplace = e.inplace;
   h->run = e.run;
   h->run_log = e.run_log;
   h->run_fast = e.run_fast;
@@ -625,6 +627,7 @@ int mxa_create_config(const mxa_config* cfg, int32_t n_envs, const uint32_t* see
   if (memcmp(&c, cfg, sizeof c) != 0) return cfg_fail("mxa_create_config: " + so + " holds another composition");
   mxa_handle* h = new mxa_handle();
   h->build = e.build;
+  h->inplace = e.inplace;
   h->run = e.run;
   h->run_log = e.run_log;
   h->run_fast = e.run_fast;
@@ -1292,6 +1295,13 @@ int mxa_read_counters(mxa_handle* h, int64_t* out) {
   HIPCHK(h, hipFreeAsync(d, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MXA_OK;
+}
+
+int mxa_read_inplace(mxa_handle* h, uint64_t* out) {
+  if (!h || !out || !h->inplace) return MXA_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return h->inplace(out) ? MXA_EHIP : MXA_OK;
 }
 
 int mxa_set_parity_hash(mxa_handle* h, int32_t enabled) {

@@ -122,6 +122,12 @@ constexpr Shape shape(int cfg);
 #ifndef MXA_LADDER_REPLIES_QUEUED
 #define MXA_LADDER_REPLIES_QUEUED 0
 #endif
+// ... and whose in-place groups ask only that no pending event sorts before the group's last pop
+// (key below (t, agent + 1)), not that none has time <= t: the market maker takes its group at the
+// instants it shares with the momentum agents (Eng::none_before, DESIGN.md §3 "The bound")
+#ifndef MXA_SYNC_BOUND_MASK
+#define MXA_SYNC_BOUND_MASK MXA_SYNC_QUERY_MASK
+#endif
 #ifndef MXA_OPEN_RFD
 #define MXA_OPEN_RFD 128
 #endif

@@ -52,10 +52,18 @@ int occupancy(size_t lds) {
   return e == hipSuccess ? n : -1;
 }
 
+// in-place group counts of this translation unit's instrumented kernels, then cleared; 0: ok
+int inplace_read(uint64_t* out) {
+  static const uint64_t z[MXA_INPLACE_WORDS] = {0};
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mxa::g_mxa_inplace), sizeof z) != hipSuccess) return 1;
+  return hipMemcpyToSymbol(HIP_SYMBOL(mxa::g_mxa_inplace), z, sizeof z) != hipSuccess;
+}
+
 template <int CFG>
 MxaEntry make_entry() {
   MxaEntry e{};
   e.build = launch_build<CFG>;
+  e.inplace = inplace_read;
   e.run = launch_run<CFG, false, true>;
   e.stop = launch_stop<CFG, false>;
   constexpr bool gym = CFG == MXA_CFG_MARKETREPLAY || CFG == MXA_CFG_RMSC03_RL;

@@ -611,6 +611,10 @@ DEV i64 U(i64 v) {
   u32 hi = (u32)__builtin_amdgcn_readfirstlane((i32)(u32)((u64)v >> 32));
   return (i64)(((u64)hi << 32) | lo);
 }
+// groups taken in place by the instrumented kernels of this translation unit's configuration, over
+// all envs since the last read (include/mxa.h mxa_read_inplace): what no env block records, since
+// an in-place group leaves the queued sequence's observables.  The plain kernels do not count
+static __device__ unsigned long long g_mxa_inplace[MXA_INPLACE_WORDS];
 #ifdef MXA_PROF
 // diagnostics build only: per-phase shader-cycle totals over all envs (tools/prof_phases.py)
 __device__ unsigned long long g_mxa_prof[128];
@@ -5081,9 +5085,10 @@ struct Eng {
   }
   // ---------------- exchange queries answered in place (zero-delay configurations)
   // POVMarketMakerAgent.wakeup sends QUERY_SPREAD and QUERY_TRANSACTED_VOLUME at its own time t; with
-  // every delay 0 they are delivered at t and answered at t.  If no other pending event has time
-  // <= t, the next four pops of Kernel.runner are forced: the two requests at the exchange (key
-  // (t, 0), seqs s, s + 1: the smallest key there is), which push only the two replies (key
+  // every delay 0 they are delivered at t and answered at t.  If no other pending event sorts
+  // before (t, mm + 1) (none_before), the next four pops of Kernel.runner are forced: the two
+  // requests at the exchange (key (t, 0), seqs s, s + 1: the smallest key there is), which push only
+  // the two replies (key
   // (t, mm), seqs s + 2, s + 3) and read the book and the header without changing them; then the
   // two replies at the market maker, the first of which pushes nothing while the agent still
   // waits for the volume (FL_AW_TV).  So the wakeup's pop does all five here, in that order, with
@@ -5092,18 +5097,34 @@ struct Eng {
   // queued sequence leaves: pops, seq, the queue's high-water mark (two more than now, twice), the
   // exchange's agentCurrentTimes, and in the instrumented kernels each elided pop's class counter,
   // parity record and hash in pop order and the two record round trips of the replies.  Anything
-  // else (another event at t, stopTime or the close behind t, a launch budget that cuts the
-  // group, a queue without two free slots, a market maker that waits for the spread alone, a
+  // else (another event before the bound, stopTime or the close behind t, a launch budget that
+  // cuts the group, a queue without two free slots, a market maker that waits for the spread alone, a
   // volume query that would raise) takes the queued path unchanged.
   static constexpr bool SYNCQ_BASE = !BUILD && RUNS && !BLOG && !MD && !RP && !TIER && PC.ex_pipeline == 0;
   static constexpr bool SYNCQ = SYNCQ_BASE && ((((MXA_SYNC_QUERY_MASK)) >> CFG) & 1) && PC.n_mm > 0;
+  // "Nothing else pending" for a group of cur_agent's at t.  The group's pops carry keys (t, 0,
+  // MESSAGE) and (t, cur_agent, MESSAGE); a pending event whose key is not below (t, cur_agent + 1)
+  // sorts after all of them whatever its seq, and touches nothing before it pops (DESIGN.md §3 "The
+  // bound").  The agent's own wakeup at t, (t, cur_agent, WAKEUP), is below the bound.  Without the
+  // mask bit: no pending event with time <= t at all.
+  static constexpr bool SYNCB = ((((MXA_SYNC_BOUND_MASK)) >> CFG) & 1) != 0;
+  // an in-place group of kind k was taken (instrumented runs: mxa_read_inplace)
+  DEV void note_inplace(int k) {
+    if constexpr (INSTR && !BUILD) {
+      if ((hash_on || trace) && lane == 0) atomicAdd(&g_mxa_inplace[k], 1ull);
+    }
+  }
+  DEV bool none_before(i64 t) {
+    const u64 bound = SYNCB ? (((u64)t << KSH) | ((u64)(cur_agent + 1) << 2)) : ((u64)(t + 1) << KSH);
+    return bal(mk < bound) == 0;
+  }
   // ---------------- the market maker's cancel and ladder runs in place
-  // At mm_requote inside mm_cycle nothing else is pending at <= t.  cancel_all's CANCEL_ORDERs and
-  // the ladder's LIMIT_ORDERs carry key (t, 0, MESSAGE), the smallest there is, and consecutive
+  // At mm_requote inside mm_cycle nothing else is pending before (t, mm + 1).  cancel_all's
+  // CANCEL_ORDERs and the ladder's LIMIT_ORDERs carry key (t, 0, MESSAGE), the smallest there is, and consecutive
   // seqs: they pop next, cancels first, and their handlers push only replies at (t, mm, MESSAGE)
   // with later seqs (no ladder order matches, so no third agent hears of it).  Those replies are
-  // then the only events at t and pop in seq order, ORDER_CANCELLED then ORDER_ACCEPTED, and
-  // neither handler pushes; the wakeup at t + mm_wake() sorts after them all.  So the same pop
+  // then the only events before the bound and pop in seq order, ORDER_CANCELLED then
+  // ORDER_ACCEPTED, and neither handler pushes; the wakeup at t + mm_wake() sorts after them all.  So the same pop
   // handles the four runs, member i in lane i, with the book code of the queued runs, and only
   // the next wakeup is pushed: into the slot it takes after cancel_all's and the ladder's batched
   // pushes (the free slot of rank nc + NL in q_push_lanes's lane-major order).  All or nothing,
@@ -5206,6 +5227,7 @@ struct Eng {
       return 0;
     }
     PROF_CNT(111);  // in-place cancel / ladder groups (of the in-place cycles)
+    note_inplace(2);
     const u64 kex = ((u64)t << KSH) | MT_MESSAGE, kmm = kex | ((u64)cur_agent << 2);
     // CANCEL_ORDER x nc at the exchange
     bool found;
@@ -5277,7 +5299,7 @@ struct Eng {
     int perr = 0;
     i64 vol = 0;
     bool ok = cur_agent < ACK_LIMIT && t <= PC.mkt_close && t <= stop_t && budget >= 5 && fl(FL_AW_TV) &&
-              qcount + 2 <= QCAP && bal((mk >> KSH) <= (u64)t) == 0;
+              qcount + 2 <= QCAP && none_before(t);
     if (ok) {
       vol = transacted_volume(lookback, &perr);
       ok = perr == 0;  // pandas would raise: the queued QUERY_TRANSACTED_VOLUME fails the env at its own pop
@@ -5288,6 +5310,7 @@ struct Eng {
       return 0;
     }
     PROF_CNT(76);  // in-place market-maker cycles (of the MM.wake calls)
+    note_inplace(0);
     const u64 kex = ((u64)t << KSH) | MT_MESSAGE, kmm = kex | ((u64)cur_agent << 2);
     if (INSTR && (hash_on || trace)) {  // the two requests as send_ex queued them
       Msg q = msg_make(MK_SPREAD_REQ, cur_agent);
@@ -5320,8 +5343,8 @@ struct Eng {
 
   // ValueAgent.wakeup (value_wakeup) likewise: cancelOrders() sends a CANCEL_ORDER for its open
   // order (a value agent holds at most one: every wake cancels, then places one) and
-  // getCurrentSpread() a QUERY_SPREAD, all to the exchange at t.  With no other event at <= t (the
-  // agent's own next wakeup, just set, included) the forced pops are: the CANCEL_ORDER and the
+  // getCurrentSpread() a QUERY_SPREAD, all to the exchange at t.  With no other event before
+  // (t, agent + 1) (the agent's own next wakeup, just set, included) the forced pops are: the CANCEL_ORDER and the
   // QUERY_SPREAD at the exchange, then ORDER_CANCELLED (if the order still rested: del orders[id],
   // the fast path of the event loop) and the spread reply at the agent, whose handler places the
   // new order.  That LIMIT_ORDER is sent as an event: it can cross and fan out executions.
@@ -5336,7 +5359,8 @@ struct Eng {
     if (lane < u && u <= 64) o = open_ptr(cur_agent)[lane];
     const u64 live = bal(o.oid != -1);
     const bool ok = status == ST_RUNNING && cur_agent < ACK_LIMIT && t <= PC.mkt_close && t <= stop_t && k <= 1 && u <= 64 &&
-                    __popcll(live) == k && budget >= 3 + 2 * k && qcount + k + 1 <= QCAP && bal((mk >> KSH) <= (u64)t) == 0;
+                    __popcll(live) == k && budget >= 3 + 2 * k && qcount + k + 1 <= QCAP &&
+                    none_before(t);
     if (!ok) {
       cancel_all();
       get_spread(1);
@@ -5344,6 +5368,7 @@ struct Eng {
       return 0;
     }
     PROF_CNT(108);  // in-place value-agent wakes (of the VALUE.wake calls)
+    note_inplace(1);
     const u64 kex = ((u64)t << KSH) | MT_MESSAGE, kag = kex | ((u64)cur_agent << 2);
     const bool instr = INSTR && (hash_on || trace);
     bool found = false;

@@ -193,6 +193,15 @@ class VecMarket:
         self._check(self.L.mxa_read_counters(self._h, out.ctypes.data), "mxa_read_counters")
         return out
 
+    def inplace_groups(self):
+        """[market-maker query groups, value-agent wakes, cancel / ladder groups, 0] taken in place by
+        the instrumented runs (parity hash on) of this configuration's handles since the last call
+        (include/mxa.h mxa_read_inplace: read, then cleared).  The env blocks cannot tell: an in-place
+        group leaves every observable of the queued sequence"""
+        out = np.zeros(_lib.INPLACE_WORDS, dtype=np.uint64)
+        self._check(self.L.mxa_read_inplace(self._h, out.ctypes.data), "mxa_read_inplace")
+        return out
+
     def write_records(self, device_ptr):
         """Per-env episode records [n][RECORD_WORDS] int64 into device memory (include/mxa.h
         mxa_write_records: events, hash, status, current_time, err, seed, last_trade, order_counter,

@@ -1,5 +1,10 @@
 #!/bin/bash
 # build rmsc03-only libmxa variants: NAME:SRCROOT:FLAGS...   (SRCROOT "." = working tree)
+# the in-place parts one by one, each on top of the previous ones:
+#   "q:.:-DMXA_SYNC_VALUE_MASK=0 -DMXA_SYNC_LADDER_MASK=0 -DMXA_SYNC_BOUND_MASK=0"   mm_cycle alone
+#   "v:.:-DMXA_SYNC_LADDER_MASK=0 -DMXA_SYNC_BOUND_MASK=0"                           + value_cycle
+#   "l:.:-DMXA_SYNC_BOUND_MASK=0"                                                    + the ladder group
+#   "b:.:"                                                                           + the tighter bound (shipped)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 pids=()
