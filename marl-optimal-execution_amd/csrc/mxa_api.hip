@@ -528,6 +528,15 @@ int mxa_config_key(const mxa_config* cfg, char* out17) {
   return MXA_OK;
 }
 
+int mxa_config_capacities(const mxa_config* cfg, int32_t out2[2]) {
+  if (!cfg || !out2) return cfg_fail("mxa_config_capacities: bad arguments");
+  if (const char* why = mxa_cfg::custom_check(*cfg)) return cfg_fail(std::string("mxa_config_capacities: ") + why);
+  const mxa_cfg::Shape S = mxa_cfg::custom_shape(*cfg);
+  out2[0] = S.sq * 64;
+  out2[1] = S.so * 64;
+  return MXA_OK;
+}
+
 int mxa_config_compile(const mxa_config* cfg, const char* cache_dir, char* path_out, int32_t path_cap) {
   if (!cfg) return cfg_fail("mxa_config_compile: null composition");
   if (const char* why = mxa_cfg::custom_check(*cfg)) return cfg_fail(std::string("mxa_config_compile: ") + why);

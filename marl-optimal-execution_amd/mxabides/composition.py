@@ -147,6 +147,17 @@ def key(cfg):
     return buf.value.decode()
 
 
+def capacities(cfg):
+    """(pending events, resting orders) per env the composition's engine is built with: the
+    requested queue_capacity / book_capacity rounded to the engine's slot rules
+    (mxa_config_capacities); ValueError for a composition compile would refuse"""
+    L = _lib.load()
+    out = (ctypes.c_int32 * 2)()
+    if L.mxa_config_capacities(ctypes.byref(cfg), out) != 0:
+        raise ValueError(L.mxa_last_error(None).decode())
+    return int(out[0]), int(out[1])
+
+
 def compile(cfg, cache_dir=None):
     """build (or find) the composition's specialised library; returns its path (mxa_config_compile)"""
     L = _lib.load()

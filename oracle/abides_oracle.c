@@ -351,6 +351,8 @@ struct ora_env {
     int used_cap, used_n;
     char sym[16]; /* the report's symbol when set (ora_set_symbol): -t/--ticker of replay configs */
     int64_t st_max_heap, st_max_resting, st_max_open, st_resting, st_max_hist_tx;
+    /* the device's per-env capacities (ora_set_capacities; 0: unbounded, the reference's own) */
+    int64_t cap_q, cap_b;
     char* report;
     int64_t report_len;
     /* Kernel.summaryLog: (agent, event type, int or float value) rows */
@@ -413,6 +415,10 @@ static int ev_less(const ev_t* a, const ev_t* b) {
     return a->seq < b->seq;
 }
 static void heap_push(ora_env* e, ev_t v) {
+    if (e->cap_q > 0 && e->nheap >= e->cap_q) { /* one pending event more than the device holds */
+        fail(e, ORA_ERR_QUEUE_FULL, "event queue over the device's capacity (ora_set_capacities)");
+        return;
+    }
     if (e->nheap == e->capheap) {
         e->capheap = e->capheap ? 2 * e->capheap : 256;
         e->heap = (ev_t*)realloc(e->heap, sizeof(ev_t) * e->capheap);
@@ -861,6 +867,10 @@ static int execute_order(ora_env* e, bord_t* order, bord_t* matched) {
 
 /* enterOrder (OrderBook.py:256-282) */
 static void enter_order(ora_env* e, bord_t o) {
+    if (e->cap_b > 0 && e->st_resting >= e->cap_b) { /* one resting order more than the device holds */
+        fail(e, ORA_ERR_BOOK_FULL, "order book over the device's capacity (ora_set_capacities)");
+        return;
+    }
     if (++e->st_resting > e->st_max_resting) e->st_max_resting = e->st_resting;
     side_t* book = &e->book[o.is_buy ? 0 : 1];
     if (book->n == 0) {
@@ -3555,6 +3565,17 @@ int ora_summary(const ora_env* e, int* agent, int* type, int* isf, int64_t* vi, 
 }
 /* capacity statistics: max pending events, max resting orders, max open orders of one agent,
  * max live transaction records */
+/* the device's capacities (include/mxa.h mxa_config_capacities) as the env's own: the push that
+ * would leave more than q pending events, or the enterOrder that would leave more than b resting
+ * orders, fails the env (the event or order is dropped, the pop's handler runs on, as on the
+ * device: pops and hash at the stop count that pop).  0 leaves a resource unbounded.  A queue the
+ * construction already overfilled fails at once. */
+void ora_set_capacities(ora_env* e, int64_t q, int64_t b) {
+    e->cap_q = q;
+    e->cap_b = b;
+    if (q > 0 && e->nheap > q) fail(e, ORA_ERR_QUEUE_FULL, "event queue over the device's capacity at construction");
+    if (b > 0 && e->st_resting > b) fail(e, ORA_ERR_BOOK_FULL, "order book over the device's capacity at construction");
+}
 void ora_stats(const ora_env* e, int64_t* out) {
     out[0] = e->st_max_heap;
     out[1] = e->st_max_resting;
@@ -3584,6 +3605,7 @@ typedef struct {
     int64_t* stats; /* optional: [n][4] ora_stats of each env */
     const ora_mm_params* mm; /* optional: rmsc03 with per-env market-maker options */
     const ora_config* cfg;   /* optional: a runtime composition */
+    int64_t cap_q, cap_b;    /* optional: ora_set_capacities of every env */
     pthread_mutex_t mu;
     int rc;
 } batch_t;
@@ -3601,6 +3623,7 @@ static void* batch_worker(void* p) {
             b->rc = -1;
             continue;
         }
+        if (b->cap_q > 0 || b->cap_b > 0) ora_set_capacities(e, b->cap_q, b->cap_b);
         ora_run(e, b->max_pops);
         b->ev[i] = e->pops;
         b->h[i] = e->hash;
@@ -3613,9 +3636,12 @@ static void* batch_worker(void* p) {
 
 static int run_batch_impl(const char* config, const uint32_t* seeds, int n, int threads, int64_t max_pops,
                           int64_t* events_out, uint64_t* hash_out, int32_t* err_out, int64_t* stats_out,
-                          double* seconds_out, const ora_mm_params* mm, const ora_config* cfg) {
+                          double* seconds_out, const ora_mm_params* mm, const ora_config* cfg, int64_t cap_q,
+                          int64_t cap_b) {
     batch_t b;
     memset(&b, 0, sizeof b);
+    b.cap_q = cap_q;
+    b.cap_b = cap_b;
     b.mm = mm;
     b.cfg = cfg;
     b.err = err_out;
@@ -3642,20 +3668,20 @@ static int run_batch_impl(const char* config, const uint32_t* seeds, int n, int 
 
 int ora_run_batch(const char* config, const uint32_t* seeds, int n, int threads, int64_t max_pops,
                   int64_t* events_out, uint64_t* hash_out, double* seconds_out) {
-    return run_batch_impl(config, seeds, n, threads, max_pops, events_out, hash_out, NULL, NULL, seconds_out, NULL, NULL);
+    return run_batch_impl(config, seeds, n, threads, max_pops, events_out, hash_out, NULL, NULL, seconds_out, NULL, NULL, 0, 0);
 }
 
 /* the same, with each env's error code (ora_error) in err_out[n] */
 int ora_run_batch_err(const char* config, const uint32_t* seeds, int n, int threads, int64_t max_pops,
                       int64_t* events_out, uint64_t* hash_out, int32_t* err_out, double* seconds_out) {
-    return run_batch_impl(config, seeds, n, threads, max_pops, events_out, hash_out, err_out, NULL, seconds_out, NULL, NULL);
+    return run_batch_impl(config, seeds, n, threads, max_pops, events_out, hash_out, err_out, NULL, seconds_out, NULL, NULL, 0, 0);
 }
 
 /* capacity statistics (ora_stats) of n envs: stats_out[n][4] */
 int ora_run_batch_stats(const char* config, const uint32_t* seeds, int n, int threads, int64_t* stats_out) {
     int64_t* ev = (int64_t*)calloc(n, sizeof(int64_t));
     uint64_t* h = (uint64_t*)calloc(n, sizeof(uint64_t));
-    int rc = run_batch_impl(config, seeds, n, threads, -1, ev, h, NULL, stats_out, NULL, NULL, NULL);
+    int rc = run_batch_impl(config, seeds, n, threads, -1, ev, h, NULL, stats_out, NULL, NULL, NULL, 0, 0);
     free(ev);
     free(h);
     return rc;
@@ -3665,13 +3691,19 @@ int ora_run_batch_config(const ora_config* c, const uint32_t* seeds, int n, int 
                          int64_t* events_out, uint64_t* hash_out, int32_t* err_out, int64_t* stats_out,
                          double* seconds_out) {
     return run_batch_impl("composition", seeds, n, threads, max_pops, events_out, hash_out, err_out, stats_out,
-                          seconds_out, NULL, c);
+                          seconds_out, NULL, c, 0, 0);
+}
+int ora_run_batch_config_cap(const ora_config* c, int64_t q, int64_t b, const uint32_t* seeds, int n, int threads,
+                             int64_t max_pops, int64_t* events_out, uint64_t* hash_out, int32_t* err_out,
+                             int64_t* stats_out, double* seconds_out) {
+    return run_batch_impl("composition", seeds, n, threads, max_pops, events_out, hash_out, err_out, stats_out,
+                          seconds_out, NULL, c, q, b);
 }
 int ora_run_batch_mm(const uint32_t* seeds, const ora_mm_params* params, int n, int threads, int64_t max_pops,
                      int64_t* events_out, uint64_t* hash_out, int32_t* err_out, int64_t* stats_out, double* seconds_out) {
     if (!params) return -1;
     return run_batch_impl("rmsc03", seeds, n, threads, max_pops, events_out, hash_out, err_out, stats_out, seconds_out,
-                          params, NULL);
+                          params, NULL, 0, 0);
 }
 
 void ora_set_book_log(ora_env* e, int on) {

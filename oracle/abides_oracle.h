@@ -74,6 +74,13 @@ int64_t ora_book(const ora_env* e, int side, int64_t* buf, int64_t cap);
 int64_t ora_order_counter(const ora_env* e);
 int64_t ora_last_trade(const ora_env* e);
 void ora_stats(const ora_env* e, int64_t* out);
+/* Opt-in: the device's per-env capacities (pending events q, resting orders b; 0 = unbounded) as
+ * the env's own.  The push / enterOrder that would exceed one fails the env with these codes, as
+ * every fail() does: the pop it happened in is counted and hashed, and nothing is popped after
+ * it.  Call after creation and before ora_run.  Without it nothing changes. */
+#define ORA_ERR_QUEUE_FULL (-20)
+#define ORA_ERR_BOOK_FULL (-21)
+void ora_set_capacities(ora_env* e, int64_t q, int64_t b);
 /* Kernel.summaryLog after ora_finish: (agent, type 0 STARTING_CASH / 1 FINAL_CASH_POSITION /
  * 2 ENDING_CASH / 3 FINAL_VALUATION, is-float, int value, float value); returns the row count */
 const char* ora_agent_type_name(const ora_env* e, int id); /* Agent.type (the summary's AgentStrategy) */
@@ -141,7 +148,7 @@ typedef struct {
     int32_t mom_min_size, mom_max_size;
     int64_t mom_wake_up_freq_ns;
     double lat_low, lat_high;
-    int32_t queue_capacity, book_capacity; /* the device's capacities (unused here) */
+    int32_t queue_capacity, book_capacity; /* the device's capacities (unused here: ora_set_capacities) */
 } ora_config;
 int ora_config_defaults(const char* base, ora_config* out);
 int ora_create_config(const ora_config* c, uint32_t seed, ora_env** out);
@@ -149,6 +156,10 @@ int ora_create_config(const ora_config* c, uint32_t seed, ora_env** out);
 int ora_run_batch_config(const ora_config* c, const uint32_t* seeds, int n, int threads, int64_t max_pops,
                          int64_t* events_out, uint64_t* hash_out, int32_t* err_out, int64_t* stats_out,
                          double* seconds_out);
+/* the same with ora_set_capacities(env, q, b) on every env */
+int ora_run_batch_config_cap(const ora_config* c, int64_t q, int64_t b, const uint32_t* seeds, int n, int threads,
+                             int64_t max_pops, int64_t* events_out, uint64_t* hash_out, int32_t* err_out,
+                             int64_t* stats_out, double* seconds_out);
 /* the ExchangeAgent's log_orders of a configuration (the exchange-log switch) */
 int ora_config_log_orders(const char* config);
 /* n GymKernel episodes, each stepped with actions[k][i][0..2] until done or error (config

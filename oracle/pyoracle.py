@@ -15,6 +15,8 @@ DEFAULT_FUND = os.path.join(os.path.dirname(HERE), "tests", "golden", "fund_JPM_
 HIST_CONFIGS = ("hist_fund_value", "hist_fund_diverse")
 _lib = None
 _fund_set = False
+# ora_set_capacities' fail() codes (abides_oracle.h)
+ERR_QUEUE_FULL, ERR_BOOK_FULL = -20, -21
 
 
 def _ensure_fundamental(config):
@@ -164,9 +166,11 @@ def config_log_orders(config):
 class OracleEnv:
     """One reference-semantics simulation (config + seed); config "rmsc03" with `mm` (one
     MM_DTYPE record) runs config/rmsc03.py with those --mm-* options; a composition (an
-    OraConfig, or a MarketConfig's bytes) runs ora_create_config."""
+    OraConfig, or a MarketConfig's bytes) runs ora_create_config.  capacities=(q, b) makes the
+    device's per-env capacities the env's own (ora_set_capacities): the push or enterOrder that
+    would exceed one fails the env with ERR_QUEUE_FULL / ERR_BOOK_FULL."""
 
-    def __init__(self, config, seed, trace_cap=0, mm=None):
+    def __init__(self, config, seed, trace_cap=0, mm=None, capacities=None):
         L = lib()
         self._h = ctypes.c_void_p()
         if not isinstance(config, str):
@@ -190,6 +194,10 @@ class OracleEnv:
         if trace_cap:
             self.trace_buf = np.zeros((trace_cap, 10), dtype=np.int64)
             L.ora_set_trace(self._h, self.trace_buf.ctypes.data, trace_cap)
+        if capacities is not None:
+            L.ora_set_capacities.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
+            L.ora_set_capacities.restype = None
+            L.ora_set_capacities(self._h, int(capacities[0]), int(capacities[1]))
 
     def run(self, max_pops=-1):
         return lib().ora_run(self._h, max_pops)
@@ -279,6 +287,16 @@ class OracleEnv:
             k += 4 * m
         return levels
 
+    def stats(self):
+        """ora_stats so far: max pending events, max resting orders, max open orders of one agent,
+        max live transaction records"""
+        L = lib()
+        L.ora_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.ora_stats.restype = None
+        out = np.zeros(4, dtype=np.int64)
+        L.ora_stats(self._h, out.ctypes.data)
+        return out
+
     @property
     def order_counter(self):
         return lib().ora_order_counter(self._h)
@@ -361,10 +379,13 @@ def batch_stats(config, seeds, threads):
     return out
 
 
-def run_batch_config(cfg, seeds, threads, max_pops=-1, stats=False):
+def run_batch_config(cfg, seeds, threads, max_pops=-1, stats=False, capacities=None):
     """one composition over many seeds: events, hashes, error codes, seconds (and [n][4] capacity
-    statistics with stats=True)"""
+    statistics with stats=True); capacities=(q, b): every env under ora_set_capacities"""
     L = lib()
+    L.ora_run_batch_config_cap.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 4 + \
+        [ctypes.POINTER(ctypes.c_double)]
     L.ora_run_batch_config.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + \
         [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_double)]
     c = as_config(cfg)
@@ -375,8 +396,14 @@ def run_batch_config(cfg, seeds, threads, max_pops=-1, stats=False):
     er = np.zeros(n, dtype=np.int32)
     st = np.zeros((n, 4), dtype=np.int64)
     sec = ctypes.c_double()
-    if L.ora_run_batch_config(ctypes.byref(c), seeds.ctypes.data, n, threads, max_pops, ev.ctypes.data, hs.ctypes.data,
-                              er.ctypes.data, st.ctypes.data if stats else None, ctypes.byref(sec)):
+    if capacities is not None:
+        rc = L.ora_run_batch_config_cap(ctypes.byref(c), int(capacities[0]), int(capacities[1]), seeds.ctypes.data, n,
+                                        threads, max_pops, ev.ctypes.data, hs.ctypes.data, er.ctypes.data,
+                                        st.ctypes.data if stats else None, ctypes.byref(sec))
+    else:
+        rc = L.ora_run_batch_config(ctypes.byref(c), seeds.ctypes.data, n, threads, max_pops, ev.ctypes.data,
+                                    hs.ctypes.data, er.ctypes.data, st.ctypes.data if stats else None, ctypes.byref(sec))
+    if rc:
         raise RuntimeError("oracle batch failed")
     return (ev, hs, er, sec.value, st) if stats else (ev, hs, er, sec.value)
 

@@ -16,7 +16,7 @@ def test_every_declared_symbol_is_exported():
     import mxabides
     L = mxabides.load()
     names = declared()
-    assert len(names) >= 18
+    assert len(names) >= 18 and "mxa_config_capacities" in names
     for n in names:
         assert hasattr(L, n), n
     assert set(names) == set(mxabides._lib.EXPORTS)
