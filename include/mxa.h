@@ -298,7 +298,10 @@ void mxa_destroy(mxa_handle* h);
 
 /* ABIDESEnv on a replay tape: n_rec time-sorted records (ns since midnight, order id > 0,
  * price in cents < 2^20, size, side 1 = buy), as LOBSTEROrdersProcessor produces them.  One
- * env per handle slot; envs differ only by the actions they are stepped with. */
+ * env per handle slot; envs differ only by the actions they are stepped with.
+ * Env errors a tape can meet: 16 a modify changing price or side, 12 auto ids
+ * beyond the dense-id range (MXA_AUTO_SKIP), 30 a QUERY_SPREAD whose best level holds more than
+ * 2^31 - 1 shares (the reply's quantity word). */
 int mxa_create_replay(const int64_t* t, const int64_t* oid, const int64_t* price, const int64_t* size,
                       const int8_t* buy, int32_t n_rec, int32_t n_envs, int32_t device, int32_t trace_cap,
                       mxa_handle** out);

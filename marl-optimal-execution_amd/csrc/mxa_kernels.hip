@@ -4097,13 +4097,20 @@ struct Eng {
     na = na < depth ? na : depth;
     Msg r = msg_make(MK_SPREAD, 0);
     i32 bb = U(R->best[0]), ab = U(R->best[1]);
+    // a level's total is 64-bit in the ladder; the reply (and its trace record) carries it in one
+    // signed 32-bit word.  The reference's Python int has no bound, so a larger total stops the env
+    const i64 bq = nb > 0 ? U(lv_qty(0)[bb]) : (i64)0, aq = na > 0 ? U(lv_qty(1)[ab]) : (i64)0;
+    if (bq > (i64)INT32_MAX || aq > (i64)INT32_MAX) {
+      fail(ERR_RP_QUOTE_SIZE);
+      return;
+    }
     if (nb > 0) {
       r.w[1] = (u32)(pmin + bb);
-      r.w[2] = (u32)U(lv_qty(0)[bb]);
+      r.w[2] = (u32)bq;
     }
     if (na > 0) {
       r.w[3] = (u32)(pmin + ab);
-      r.w[4] = (u32)U(lv_qty(1)[ab]);
+      r.w[4] = (u32)aq;
     }
     i32 b2 = 0, a2 = 0;
     if (nb > 1) b2 = pmin + lvl_next(0, bb - 1);

@@ -94,7 +94,11 @@ enum {
   ERR_SB_MID = 28,
   // an order quantity beyond the device's 32-bit order words (POVMarketMakerAgent: pov x transacted
   // volume with a large --mm-pov); the reference's Python int has no bound, so the env stops
-  ERR_ORDER_SIZE = 29
+  ERR_ORDER_SIZE = 29,
+  // marketreplay / ABIDESEnv: a QUERY_SPREAD reply whose best level's total quantity is beyond the
+  // reply's signed 32-bit quantity word (the ladder keeps 64-bit totals; the reference quotes a
+  // Python int)
+  ERR_RP_QUOTE_SIZE = 30
 };
 
 // per-env scalar header (first bytes of the env block)
