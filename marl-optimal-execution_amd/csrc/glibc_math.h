@@ -19,11 +19,27 @@
 #include <hip/hip_runtime.h>
 #define GM_FN __host__ __device__ __forceinline__ static
 #define GM_BIG __host__ __device__ __forceinline__ static
+// The tables are constant-initialised statics that device code uses directly: the compiler emits a
+// private copy of each next to the device code and reaches it pc-relatively, one scalar load per
+// read.  As `static __device__ __constant__` variables HIP made them externally visible (the host
+// can name a __constant__), and position-independent code then read every table address from the
+// GOT first: two dependent scalar-memory round trips where one is needed.  -DGM_TABLES_GOT restores
+// that form (the A/B variant of DESIGN.md Appendix R.10).
+#ifdef GM_TABLES_GOT
 #define GM_TABLE_QUAL static __device__ __constant__ const
+#else
+#define GM_TABLE_QUAL static constexpr
+#endif
 #else
 #define GM_FN static inline
 #define GM_BIG static inline
 #define GM_TABLE_QUAL static const
+#endif
+
+// the special-range tests below (arguments no draw of the engine produces but at its edges); the
+// including unit may define it as a branch weight (mxa_kernels.hip), the default is the plain test
+#ifndef GM_UNLIKELY
+#define GM_UNLIKELY(x) (x)
 #endif
 
 #include "glibc_math_tables.h"
@@ -36,7 +52,7 @@ GM_BIG double gm_log(double x) {
   uint64_t ix = gm_asu64(x);
   uint32_t top = (uint32_t)(ix >> 48);
   const uint64_t LO = 0x3fee000000000000ull, HI = 0x3ff1090000000000ull;
-  if (ix - LO < HI - LO) {
+  if (GM_UNLIKELY(ix - LO < HI - LO)) {
     if (ix == 0x3ff0000000000000ull) return 0.0;
     double r = x - 1.0;
     double r2 = r * r;
@@ -61,7 +77,7 @@ GM_BIG double gm_log(double x) {
     double y = __builtin_fma(q, r3, lo);
     return hi + y;
   }
-  if (top - 0x0010u >= 0x7ff0u - 0x0010u) {
+  if (GM_UNLIKELY(top - 0x0010u >= 0x7ff0u - 0x0010u)) {
     if (ix * 2 == 0) return -__builtin_inf();
     if (ix == 0x7ff0000000000000ull) return x;
     if ((top & 0x8000u) || (top & 0x7ff0u) == 0x7ff0u) return __builtin_nan("");
@@ -114,7 +130,7 @@ GM_FN double gm_exp_special(double tmp, uint64_t sbits, uint64_t ki) {
 GM_BIG double gm_exp(double x) {
   uint64_t ix = gm_asu64(x);
   uint32_t abstop = (uint32_t)(ix >> 52) & 0x7ffu;
-  if (abstop - 0x3c9u > 0x3eu) {
+  if (GM_UNLIKELY(abstop - 0x3c9u > 0x3eu)) {
     if ((int32_t)(abstop - 0x3c9u) < 0) return x + 1.0;
     if (abstop >= 0x409u) {
       if (ix == 0xfff0000000000000ull) return 0.0;
@@ -139,7 +155,7 @@ GM_BIG double gm_exp(double x) {
   p = __builtin_fma(p, r2, t);
   double r4 = r2 * r2;
   double tmp = __builtin_fma(r4, q, p);
-  if (abstop == 0) return gm_exp_special(tmp, sbits, ki);
+  if (GM_UNLIKELY(abstop == 0)) return gm_exp_special(tmp, sbits, ki);
   double scale = gm_asf64(sbits);
   return __builtin_fma(scale, tmp, scale);
 }
@@ -181,7 +197,7 @@ GM_BIG double gm_pow(double x, double y) {
   uint32_t sign_bias = 0;
   uint64_t ix = gm_asu64(x), iy = gm_asu64(y);
   uint32_t topx = (uint32_t)(ix >> 52), topy = (uint32_t)(iy >> 52);
-  if (topx - 0x001u >= 0x7ffu - 0x001u || (topy & 0x7ffu) - 0x3beu >= 0x43eu - 0x3beu) {
+  if (GM_UNLIKELY(topx - 0x001u >= 0x7ffu - 0x001u || (topy & 0x7ffu) - 0x3beu >= 0x43eu - 0x3beu)) {
     if (gm_zeroinfnan(iy)) {
       if (2 * iy == 0) return 1.0;
       if (ix == 0x3ff0000000000000ull) return 1.0;
@@ -250,7 +266,7 @@ GM_BIG double gm_pow(double x, double y) {
   // exp_inline(ehi, elo, sign_bias)
   uint64_t ie = gm_asu64(ehi);
   uint32_t abstop = (uint32_t)(ie >> 52) & 0x7ffu;
-  if (abstop - 0x3c9u > 0x3eu) {
+  if (GM_UNLIKELY(abstop - 0x3c9u > 0x3eu)) {
     if ((int32_t)(abstop - 0x3c9u) < 0) {
       double one = ehi + 1.0;
       return sign_bias ? -one : one;
@@ -278,7 +294,7 @@ GM_BIG double gm_pow(double x, double y) {
   p = __builtin_fma(p, r2, t);
   double r4 = r2 * r2;
   double etmp = __builtin_fma(r4, q, p);
-  if (abstop == 0) return gm_pow_special(etmp, sbits, ki);
+  if (GM_UNLIKELY(abstop == 0)) return gm_pow_special(etmp, sbits, ki);
   double scale = gm_asf64(sbits);
   return __builtin_fma(scale, etmp, scale);
 }

@@ -128,6 +128,11 @@ constexpr Shape shape(int cfg);
 #ifndef MXA_SYNC_BOUND_MASK
 #define MXA_SYNC_BOUND_MASK MXA_SYNC_QUERY_MASK
 #endif
+// 1: Eng::value_cycle loads the agent's open-order chunk before the wakeup's head instead of after
+// it
+#ifndef MXA_VALUE_OPEN_EARLY
+#define MXA_VALUE_OPEN_EARLY 0
+#endif
 #ifndef MXA_OPEN_RFD
 #define MXA_OPEN_RFD 128
 #endif

@@ -27,6 +27,48 @@
 #define MXA_NO_GYM
 #endif
 
+// Branch weights of the event loop (DESIGN.md §5 "Branch weights" has the table of hints).  The loop
+// is one inlined function whose spill weights, live-range splits and block order the compiler takes
+// from block frequencies; without weights those are static guesses.  MXA_LIKELY / MXA_UNLIKELY
+// (error returns and fall-back paths) and MXA_RARE / MXA_RARE_P (RNG and math branches taken once
+// in many draws) state them for the configurations of MXA_HINT_MASK (bit = config id: the unit's
+// -DMXA_INST_CFG, or a single-configuration variant build's); every other unit compiles the plain
+// condition.  Only wave-uniform branches carry one: a divergent branch is structurized and ignores
+// it.  MXA_HINT_GROUPS (bit 0 errors and fall-backs, bit 1 RNG and math) builds the A/B variants of
+// DESIGN.md Appendix R.10; weights on the loop's own dispatch order were measured there and lost.
+#ifndef MXA_HINT_MASK
+#define MXA_HINT_MASK ((1 << 0) | (1 << 4))  // MXA_CFG_RMSC03, MXA_CFG_RMSC03_RL
+#endif
+#ifndef MXA_HINT_GROUPS
+#define MXA_HINT_GROUPS 3
+#endif
+#if defined(MXA_INST_CFG)
+#define MXA_HINT_ON (((MXA_HINT_MASK) >> (MXA_INST_CFG)) & 1)
+#elif defined(MXA_ONLY_RMSC03) && defined(MXA_ONLY_CFG)
+#define MXA_HINT_ON (((MXA_HINT_MASK) >> (MXA_ONLY_CFG)) & 1)
+#elif defined(MXA_ONLY_RMSC03)
+#define MXA_HINT_ON ((MXA_HINT_MASK) & 1)
+#else
+#define MXA_HINT_ON 0
+#endif
+#define MXA_EXPECT_(x, v) __builtin_expect(!!(x), v)  // (!!: many conditions are 64-bit ballots)
+#define MXA_PROB_(x, v, p) __builtin_expect_with_probability(!!(x), v, p)
+#if MXA_HINT_ON && ((MXA_HINT_GROUPS) & 1)
+#define MXA_LIKELY(x) MXA_EXPECT_(x, 1)
+#define MXA_UNLIKELY(x) MXA_EXPECT_(x, 0)
+#else
+#define MXA_LIKELY(x) (x)
+#define MXA_UNLIKELY(x) (x)
+#endif
+#if MXA_HINT_ON && ((MXA_HINT_GROUPS) & 2)
+#define MXA_RARE(x) MXA_EXPECT_(x, 0)
+#define MXA_RARE_P(x, p) MXA_PROB_(x, 1, p)  // true with probability p
+#define GM_UNLIKELY(x) MXA_EXPECT_(x, 0)
+#else
+#define MXA_RARE(x) (x)
+#define MXA_RARE_P(x, p) (x)
+#endif
+
 #include "../../include/mxa.h"
 #include "glibc_math.h"
 #include "mxa_layout.h"
@@ -313,7 +355,7 @@ DEV u32 rs_u32(RSt<B>& r) {
   if constexpr (!B || MXA_BUILD_WINDOWS) {
     if (r.lw) {
       u32 off = (u32)(r.p - r.lw0);
-      if (off >= (u32)r.lwn) {
+      if (MXA_RARE(off >= (u32)r.lwn)) {  // the window refill: one word in 64
         if constexpr (B) {  // the build materializes blocks as it draws
           const int blk = r.p / MXA_MT_N;
           while (r.m < blk) {
@@ -366,7 +408,7 @@ DEV i64 rs_randint(RSt<B>& r, i64 lo, i64 hi) {
   u32 v;
   do {
     v = rs_u32(r) & mask;
-  } while (v > (u32)rng);
+  } while (MXA_RARE(v > (u32)rng));  // (below one half whatever the range: the mask is its next 2^k - 1)
   return lo + (i64)v;
 }
 // the run kernel's normal draws (numpy legacy_gauss).  A wave-parallel form (16 polar
@@ -390,7 +432,7 @@ DEV double rs_gauss_serial(RSt<B>& r) {
     x1 = 2.0 * rs_double(r) - 1.0;
     x2 = 2.0 * rs_double(r) - 1.0;
     r2 = x1 * x1 + x2 * x2;
-  } while (r2 >= 1.0 || r2 == 0.0);
+  } while (MXA_RARE_P(r2 >= 1.0 || r2 == 0.0, 0.215));  // the polar method rejects 1 - pi / 4
   f = __builtin_sqrt(-2.0 * gm_log(r2) / r2);
   r.gauss = f * x1;
   r.hasg |= 1;
@@ -1158,9 +1200,9 @@ struct Eng {
       const bool kr = KREG && k == KS;
       const i32 p = kr ? kp : k < 4 ? h.rs_pos[k] : rgi(AF_RS_POS), m = kr ? km : k < 4 ? h.rs_m[k] : rgi(AF_RS_M);
       const i32 hg = kr ? khg : k < 4 ? h.rs_has_gauss[k] : rgi(AF_RS_HASG);
-      if (hg & 2) fail(ERR_RNG_OVERRUN);
+      if (MXA_UNLIKELY(hg & 2)) fail(ERR_RNG_OVERRUN);
       const int la = k < 4 ? MXA_MT_N : MXA_AGENT_LA;
-      if (m >= (p + la) / MXA_MT_N) continue;  // the look-ahead is there (almost always)
+      if (!MXA_RARE(m < (p + la) / MXA_MT_N)) continue;  // the look-ahead is there (almost always)
       RS r = kr ? grs_k() : k < 4 ? grs(k) : agent_rs();
       rs_maint(r, la);
       if (kr) {
@@ -1475,7 +1517,7 @@ struct Eng {
       if (bal(use != 0) == 0) use = qfree;
     }
     u64 b = bal(use != 0);
-    if (b == 0) {
+    if (MXA_UNLIKELY(b == 0)) {
       fail(ERR_QUEUE_FULL);
       return;
     }
@@ -1525,7 +1567,7 @@ struct Eng {
       base += (int)__builtin_amdgcn_mbcnt_hi((u32)(b >> 32), __builtin_amdgcn_mbcnt_lo((u32)b, 0u));
       total += __popcll(b);
     }
-    if (total < n) {
+    if (MXA_UNLIKELY(total < n)) {
       fail(ERR_QUEUE_FULL);
       return;
     }
@@ -1675,7 +1717,7 @@ struct Eng {
   }
   // Kernel.setWakeup (Kernel.py:435-462)
   DEV void wakeup_at(int agent, i64 t) {
-    if (t < cur) {
+    if (MXA_UNLIKELY(t < cur)) {
       fail(ERR_WAKEUP_PAST);
       return;
     }
@@ -1772,7 +1814,7 @@ struct Eng {
     i64 pt = h.o_pt;
     double pv = h.o_pv;
     if (t <= pt) return pv;
-    while (h.o_mst < t) {
+    while (MXA_RARE(h.o_mst < t)) {  // a megashock: one an hour (1 / o_lambda)
       double v = o_compute(h.o_mst, h.o_msv, pt, pv);
       pt = h.o_mst;
       pv = v;
@@ -1919,7 +1961,7 @@ struct Eng {
   }
   DEV void b_enter(i32 oid, i32 agent, int is_buy, i32 qty, i32 price, i32 hep, i32 ridx = 0) {
     int s = b_free_slot();
-    if (s < 0) {
+    if (MXA_UNLIKELY(s < 0)) {
       fail(ERR_BOOK_FULL);
       return;
     }
@@ -1949,7 +1991,7 @@ struct Eng {
     int pos = h.tx_head % cap;
     if (h.tx_head >= cap) {  // overwriting the oldest record: it must be dead
       TxRec old = R[pos];
-      if (old.epoch >= h.epoch - PC.stream_history) {
+      if (MXA_UNLIKELY(old.epoch >= h.epoch - PC.stream_history)) {
         fail(ERR_TX_FULL);
         return;
       }
@@ -2412,7 +2454,7 @@ struct Eng {
     case MK_TV_REQ: {
       int perr = 0;
       i64 vol = transacted_volume(m_i64(m, 1), &perr);
-      if (perr) {
+      if (MXA_UNLIKELY(perr)) {
         fail(ERR_PANDAS_NO_TX);
         return;
       }
@@ -2484,13 +2526,13 @@ struct Eng {
   DEV void place_limit_oid(i64 qty, int is_buy, i64 price, i64 oid) {
     if (qty > 0) {
       i32 n = rgi(AF_NORD);
-      if (n >= PC.L.open_cap) {
+      if (MXA_UNLIKELY(n >= PC.L.open_cap)) {
         fail(ERR_OPEN_FULL);
         return;
       }
       OpenOrder* oo = open_ptr(cur_agent);
       i32 u = rgi(AF_NUSED);
-      if (u >= PC.L.open_cap) u = open_compact();
+      if (MXA_UNLIKELY(u >= PC.L.open_cap)) u = open_compact();
       if (lane == 0) {
         OpenOrder o;
         o.oid = (i32)oid;
@@ -2983,7 +3025,7 @@ struct Eng {
     if (k == MK_TV && fl(FL_AW_TV)) {
       i64 qty = py_round(mm_pov() * (double)rg64(AF_TV));
       const i64 mn = mm_min();
-      if (qty > INT32_MAX) {  // the order words are 32-bit: stop loudly, never wrap
+      if (MXA_UNLIKELY(qty > INT32_MAX)) {  // the order words are 32-bit: stop loudly, never wrap
         fail(ERR_ORDER_SIZE);
         return false;
       }
@@ -3031,7 +3073,7 @@ struct Eng {
     if constexpr (!PC.mm_rt) {  // the script's constant ladder: one pass (the measured rmsc03 code)
       constexpr int CNB = PC.mm_ticks + 1, CNL = 2 * CNB;
       i32 u = rgi(AF_NUSED);
-      if (u + CNL > PC.L.open_cap) u = open_compact();
+      if (MXA_UNLIKELY(u + CNL > PC.L.open_cap)) u = open_compact();
       const bool act = lane < CNL;
       const int buy = lane < CNB;
       const i32 price = (i32)(buy ? lb + lane : la + (lane - CNB));
@@ -4619,7 +4661,7 @@ struct Eng {
         }
       } else if (ty == AG_VALUE || ty == AG_ZI || ty == AG_HBL) {  // HBL inherits ZI.kernelStopping
         const i64 rT = o_observe(rg64(AF_ATIME) - rg64(AF_COMP), 0.0);
-        if (dirty) rng_maint();
+        if (MXA_RARE(dirty)) rng_maint();
         f.final_fundamental = rT;
         if (ty == AG_VALUE) {
           f.kind = 2;
@@ -5229,7 +5271,7 @@ struct Eng {
       wl = ok ? ctz64(lb_) : 0;
       wj = (int)rdl((u32)(f ? qm_ctz(f) : 0), wl);
     }
-    if (!ok) {
+    if (MXA_UNLIKELY(!ok)) {
       mm_requote(mid);
       return 0;
     }
@@ -5311,7 +5353,7 @@ struct Eng {
       vol = transacted_volume(lookback, &perr);
       ok = perr == 0;  // pandas would raise: the queued QUERY_TRANSACTED_VOLUME fails the env at its own pop
     }
-    if (!ok) {
+    if (MXA_UNLIKELY(!ok)) {
       get_spread(1);
       get_tv(lookback);
       return 0;
@@ -5358,17 +5400,27 @@ struct Eng {
   // More than one open order, or a list longer than one 64-entry chunk, takes the queued path.
   static constexpr bool SYNCV = SYNCQ_BASE && ((((MXA_SYNC_VALUE_MASK)) >> CFG) & 1) && PC.n_value > 0;
   DEV int value_cycle(i64 t, i64 budget) {
-    if (!value_wake_head()) return 0;
-    const i32 u = rgi(AF_NUSED), k = rgi(AF_NORD);
+    // the open-order chunk needs only cur_agent and AF_NUSED, which the head of the wakeup leaves as
+    // they are (it draws the next wake time and pushes the wakeup; the list changes at orders and
+    // acknowledgements only): MXA_VALUE_OPEN_EARLY issues its load before the head's dependent
+    // stream read instead of after it.  A load wasted on a wakeup that ends in its head is harmless
     OpenOrder o;
     o.oid = -1;
     o.is_buy = o.qty = o.price = 0;
-    if (lane < u && u <= 64) o = open_ptr(cur_agent)[lane];
+    if constexpr (MXA_VALUE_OPEN_EARLY != 0) {
+      const i32 u0 = rgi(AF_NUSED);
+      if (lane < u0 && u0 <= 64) o = open_ptr(cur_agent)[lane];
+    }
+    if (!value_wake_head()) return 0;
+    const i32 u = rgi(AF_NUSED), k = rgi(AF_NORD);
+    if constexpr (MXA_VALUE_OPEN_EARLY == 0) {
+      if (lane < u && u <= 64) o = open_ptr(cur_agent)[lane];
+    }
     const u64 live = bal(o.oid != -1);
     const bool ok = status == ST_RUNNING && cur_agent < ACK_LIMIT && t <= PC.mkt_close && t <= stop_t && k <= 1 && u <= 64 &&
                     __popcll(live) == k && budget >= 3 + 2 * k && qcount + k + 1 <= QCAP &&
                     none_before(t);
-    if (!ok) {
+    if (MXA_UNLIKELY(!ok)) {
       cancel_all();
       get_spread(1);
       rs(AF_STATE, AS_AWAITING_SPREAD);
@@ -5407,7 +5459,7 @@ struct Eng {
     account_pop(t, kag, r);
     if (instr && lane == 0) h.kc[MXA_KC_REC] += found ? 2 : 1;  // the replies' record round trips
     rs(AF_STATE, AS_AWAITING_SPREAD);
-    if (dirty) rng_maint();  // the wakeup's own event boundary, before the reply's draws
+    if (MXA_RARE(dirty)) rng_maint();  // the wakeup's own event boundary, before the reply's draws
     value_receive(r);
     return np;
   }
@@ -5434,7 +5486,7 @@ struct Eng {
       u64 key;
       u32 eseq;
       int slot = q_peek(key, eseq);
-      if (slot < 0 || !(cur <= stop_t)) {
+      if (MXA_UNLIKELY(slot < 0 || !(cur <= stop_t))) {
         status = ST_DONE;
         break;
       }
@@ -5493,7 +5545,7 @@ struct Eng {
             PROF_CNT(eb + 8);
           }
 #endif
-          if (dirty) rng_maint();
+          if (MXA_RARE(dirty)) rng_maint();
           PROF_ADD(30, t0);
           atime_store(0, t);
           PROF_ADD(31, t0);
@@ -5571,13 +5623,13 @@ struct Eng {
         if (type == MT_CANCEL_ORDER) {  // GymKernel CANCEL_ORDER: no busy check, no delay
           q_remove(slot);
           rl_kernel_cancel();
-          if (dirty) rng_maint();
+          if (MXA_RARE(dirty)) rng_maint();
           continue;
         }
       }
       i64 at = rg64(AF_ATIME);
       PROF_ADD(0, t0);
-      if (at > t) {  // agent in the future: requeue unchanged (same uniq)
+      if (MXA_UNLIKELY(at > t)) {  // agent in the future: requeue unchanged (same uniq)
         q_rekey(slot, ((u64)at << KSH) | (key & ((1ull << KSH) - 1)));
         if (INSTR && (hash_on || trace) && lane == 0) h.kc[MXA_KC_REQUEUE]++;
         PROF_ADD(1, t0);
@@ -5616,7 +5668,7 @@ struct Eng {
       else dispatch(rgi(AF_TYPE), type == MT_WAKEUP, m);
       PROF_ADD(pb, t0);
       PROF_CNT(pc);
-      if (dirty) rng_maint();
+      if (MXA_RARE(dirty)) rng_maint();
       PROF_ADD(30, t0);
       rs64(AF_ATIME, t + rg64(AF_COMP) + add_delay);
       rec_store();
