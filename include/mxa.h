@@ -33,6 +33,10 @@
  *                        (GymKernel.py:158-306) with DummyRL.place_orders/get_observation
  *                        (dummy_rl_execution_agent.py:138-179, 291-312)
  *   mxa_step_many ...... k ABIDESEnv.step calls in a row with the actions given up front, one launch
+ *   mxa_step_policy .... k periods of DDQLearningExecutionAgent in one launch: choose_action
+ *                        (ddqlearning_execution_agent.py:333-362) on the env's own observation,
+ *                        take_action (:364-407), then ABIDESEnv.step (ABIDESEnv.py:30-49)
+ *   mxa_policy_probe ... (parity tooling: choose_action's forward, argmax and select on given rows)
  */
 #ifndef MXA_H
 #define MXA_H
@@ -332,6 +336,37 @@ int mxa_step_device(mxa_handle* h, const double* d_actions, double* d_obs, int32
  * its steps without waiting for the slowest env of each step.  Asynchronous on the handle's
  * stream; GymKernel handles only (MXA_EINVAL otherwise). */
 int mxa_step_many(mxa_handle* h, int32_t k, const double* d_actions, double* d_obs, int32_t* d_flags);
+/* the DDQN execution learner's policy (mxabides.ddqn DDQNLearner + ExecutionTask), evaluated inside
+ * the step kernel: the Q-network's flat fp32 parameters as mxa_qnet_* take them (include/mxa_ddqn.h:
+ * per layer weight[out][in] row-major, then bias[out]; 1..8 layers of 1..256 units, dims[0] == 2),
+ * the state grid's split points, the action table and choose_action's exploration inputs.  Every
+ * pointer is a DEVICE pointer; dims, the lengths and the scalars are host values. */
+typedef struct mxa_policy {
+  const float* params; int32_t n_layers; int32_t dims[9];
+  const double* grid0; int32_t n0; const double* grid1; int32_t n1;
+  double nh, q0;        /* ExecutionTask: horizon points, parent quantity */
+  const double* table;  /* [dims[n_layers]][3] action vectors */
+  int32_t test, enough; /* mode == "test"; the replay holds a batch (constant over the launch) */
+  const double* u; const int64_t* rnd; /* [k][n_envs] choose_action's draws; unread when test */
+  const double* eps;    /* scalar (f64); unread when test */
+} mxa_policy;
+/* k periods of every env in one launch with the epsilon-greedy Q-network policy evaluated in place
+ * (choose_action, ddqlearning_execution_agent.py:333-362; take_action, :364-407; ABIDESEnv.step,
+ * ABIDESEnv.py:30-49).  Step i of an env: x = ExecutionTask.state of the env's own stored
+ * observation (the one its previous step returned), q = forward(x) on the env's wave, greedy =
+ * argmax(q), a = (!test && !(u[i][e] < *eps && enough)) ? rnd[i][e] : greedy, act =
+ * ExecutionTask.actions(a, obs), then the step with act.  Bit for bit the sequence mxa_ddqn_state,
+ * mxa_qnet_act, mxa_step_device, mxa_write_rl_state per period.  DEVICE outputs: d_obs [k][n][9],
+ * d_flags [k][n] (as mxa_step_many), d_a [k][n] int64 action indices, d_act [k][n][3] action
+ * vectors, d_state [k][n][MXA_RL_STATE_WORDS] (mxa_write_rl_state's row after the step; nullable).
+ * Finished and errored envs keep their state and still get their rows, from the sticky observation.
+ * first_zero: step 0 of the launch places (0, 0, 0) without consulting the policy (run_episode's
+ * first step); its d_a row is -1 and row 0 of u / rnd is not read.  Asynchronous on the handle's
+ * stream.  MXA_EINVAL before any HIP call: not a GymKernel handle, k <= 0, a null required
+ * pointer, !test with a null u, rnd or eps, dimensions outside 1..8 layers of 1..256 units,
+ * dims[0] != 2, a negative grid length. */
+int mxa_step_policy(mxa_handle* h, int32_t k, int32_t first_zero, const mxa_policy* p, double* d_obs,
+                    int32_t* d_flags, int64_t* d_a, double* d_act, double* d_state);
 /* the per-pop parity hash (mxa_env_summary.hash: a rolling FNV-1a over every pop's trace
  * record, the test harness's checksum; the reference computes nothing like it) is on by
  * default.  Turning it off leaves every market result identical and the hash field frozen at
@@ -404,6 +439,14 @@ int mxa_read_book_log(mxa_handle* h, int32_t env, mxa_book_rec* out, int64_t cap
  * 2 pow) */
 int mxa_rng_probe(int32_t device, uint32_t seed, int32_t mode, double a, double b, int32_t n, double* out);
 int mxa_math_probe(int32_t device, int32_t mode, const double* x, const double* y, double* out, int64_t n);
+/* the policy of mxa_step_policy on given input rows, one wave per row: choose_action's forward,
+ * argmax and select (ddqlearning_execution_agent.py:333-362) with any dims[0] in 1..256.  DEVICE
+ * arrays on the current device, asynchronous on `stream` (a hipStream_t; null: the default stream):
+ * x [n][dims[0]] fp32 -> q [n][dims[n_layers]] fp32 (nullable), a [n] int64 (nullable); test,
+ * enough, u [n], rnd [n], eps as in mxa_policy. */
+int mxa_policy_probe(void* stream, int32_t n, const float* x, const float* params, int32_t n_layers,
+                     const int32_t* dims, int32_t test, int32_t enough, const double* u, const int64_t* rnd,
+                     const double* eps, float* q, int64_t* a);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ OUT = os.path.join(HERE, "lib", "libmxa.so")
 OBJ = os.path.join(HERE, "build")
 N_CONFIGS = 18  # csrc/mxa_entry.h MXA_N_CONFIGS
 DEPS = ["mxa_api.hip", "mxa_inst.hip", "mxa_entry.h", "mxa_kernels.hip", "mxa_layout.h", "mxa_config.h", "glibc_math.h",
-        "glibc_math_tables.h"]
+        "glibc_math_tables.h", "qnet_wave_device.h", "ddqn_device.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -structurizecfg-skip-uniform-regions: branches on wave-uniform conditions stay plain scalar
 # branches instead of being structurized into exec-mask regions (saveexec / restore pairs and

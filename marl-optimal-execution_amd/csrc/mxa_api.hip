@@ -209,6 +209,7 @@ struct mxa_handle {
   mxa_run_fn run_fast = nullptr;                   // hash off, no trace ring: instrumentation compiled out
   mxa_step_fn step = nullptr, step_fast = nullptr;  // GymKernel handles (replay, rmsc03_rl)
   mxa_step_many_fn step_many = nullptr, step_many_fast = nullptr;  // k steps per launch
+  mxa_step_policy_fn step_policy = nullptr, step_policy_fast = nullptr;  // k periods per launch, policy in place
   mxa_stop_fn stop = nullptr, stop_log = nullptr;  // kernelStopping pass (plain Kernel.runner configs)
   mxa_agent_final* d_final = nullptr;
   BlRec* d_blog = nullptr;  // book-update log [n_envs][blog_cap] (mxa_set_book_log)
@@ -299,6 +300,8 @@ static bool bind(mxa_handle* h, int cfg) {
   h->step_fast = e.step_fast;
   h->step_many = e.step_many;
   h->step_many_fast = e.step_many_fast;
+  h->step_policy = e.step_policy;
+  h->step_policy_fast = e.step_policy_fast;
   h->gym = e.step != nullptr;
   h->occ = e.occ;
   h->lds = mxa_cfg::lds_bytes(cfg);
@@ -907,6 +910,30 @@ int mxa_step_many(mxa_handle* h, int32_t k, const double* d_actions, double* d_o
 #endif
 }
 
+// k periods in one launch with the epsilon-greedy Q-network policy evaluated in the step kernel
+// (include/mxa.h): every argument is checked before the first HIP call
+int mxa_step_policy(mxa_handle* h, int32_t k, int32_t first_zero, const mxa_policy* p, double* d_obs, int32_t* d_flags,
+                    int64_t* d_a, double* d_act, double* d_state) {
+  if (!h || !h->gym || k <= 0 || !p || !d_obs || !d_flags || !d_a || !d_act) return MXA_EINVAL;
+  if (!p->params || !p->grid0 || !p->grid1 || !p->table || p->n0 < 0 || p->n1 < 0) return MXA_EINVAL;
+  if (!p->test && (!p->u || !p->rnd || !p->eps)) return MXA_EINVAL;
+  if (!qwave::dims_ok(p->n_layers, p->dims) || p->dims[0] != 2) return MXA_EINVAL;
+  if (d_state && h->P.n_rl != 1) return MXA_EINVAL;  // the rl-state row is the one execution agent's
+#ifdef MXA_NO_GYM
+  return MXA_EINVAL;
+#else
+  if (!h->step_policy) return MXA_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  (h->tcap_arg() < 0 && h->step_policy_fast ? h->step_policy_fast : h->step_policy)(
+      dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, h->P.n_envs, h->tcap_arg(),
+      (int64_t)1 << 40, (const RpCtx*)h->d_ctx, *p, d_obs, d_flags, d_a, d_act, d_state, k, first_zero != 0);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  return MXA_OK;
+#endif
+}
+
 // the same with device arrays (e.g. torch tensors), asynchronous on the handle's stream
 int mxa_step_device(mxa_handle* h, const double* d_actions, double* d_obs, int32_t* d_flags) {
   if (!h || !h->gym) return MXA_EINVAL;
@@ -1412,6 +1439,24 @@ int mxa_math_probe(int32_t device, int32_t mode, const double* x, const double* 
   hipFree(dy);
   hipFree(dout);
   return e == hipSuccess ? MXA_OK : MXA_EHIP;
+}
+
+int mxa_policy_probe(void* stream, int32_t n, const float* x, const float* params, int32_t n_layers, const int32_t* dims,
+                     int32_t test, int32_t enough, const double* u, const int64_t* rnd, const double* eps, float* q,
+                     int64_t* a) {
+  if (n <= 0 || !x || !params || !qwave::dims_ok(n_layers, dims) || (!q && !a)) return MXA_EINVAL;
+  if (a && !test && (!u || !rnd || !eps)) return MXA_EINVAL;
+  MxaPolicyProbe p{};
+  p.params = params;
+  p.n_layers = n_layers;
+  for (int i = 0; i <= n_layers; i++) p.dims[i] = dims[i];
+  p.test = test;
+  p.enough = enough;
+  p.u = u;
+  p.rnd = rnd;
+  p.eps = eps;
+  hipLaunchKernelGGL(mxa_policy_probe_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, p, n, x, q, a);
+  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_EHIP;
 }
 
 }  // extern "C"

@@ -21,6 +21,11 @@ typedef void (*mxa_step_fn)(dim3, dim3, size_t, hipStream_t, char*, uint64_t, in
 typedef void (*mxa_step_many_fn)(dim3, dim3, size_t, hipStream_t, char*, uint64_t, int, int, int64_t, const RpCtx*,
                                  const double*, double*, int32_t*, int);
 
+// the closed-loop flavour (mxa_step_policy): the policy POD by value, then obs, flags, action
+// indices, action vectors, rl-state rows (nullable), k, first_zero
+typedef void (*mxa_step_policy_fn)(dim3, dim3, size_t, hipStream_t, char*, uint64_t, int, int, int64_t, const RpCtx*,
+                                   const mxa_policy&, double*, int32_t*, int64_t*, double*, double*, int, int);
+
 typedef int (*mxa_inplace_fn)(uint64_t*);  // read and clear the configuration's in-place group counts (mxa_read_inplace)
 typedef int (*mxa_occ_fn)(size_t);  // resident blocks (envs) per CU of the measured kernel at that LDS size
 
@@ -31,6 +36,7 @@ struct MxaEntry {
   mxa_stop_fn stop, stop_log;
   mxa_step_fn step, step_fast; // GymKernel configurations (step_fast: without the instrumentation)
   mxa_step_many_fn step_many, step_many_fast;  // k steps per launch, actions given up front
+  mxa_step_policy_fn step_policy, step_policy_fast;  // k periods per launch, the Q-network policy in place
   mxa_inplace_fn inplace;      // g_mxa_inplace of the configuration's translation unit
   mxa_occ_fn occ;              // hipOccupancyMaxActiveBlocksPerMultiprocessor of run_fast / step_fast
 };

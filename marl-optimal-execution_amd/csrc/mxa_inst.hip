@@ -38,6 +38,14 @@ void launch_step_many(dim3 g, dim3 b, size_t lds, hipStream_t s, char* base, uin
   hipLaunchKernelGGL((mxa_step_kernel<CFG, INSTR, true>), g, b, lds, s, base, stride, n, tcap, max_pops, ctx, act, obs,
                      flags, k);
 }
+template <int CFG, bool INSTR>
+void launch_step_policy(dim3 g, dim3 b, size_t lds, hipStream_t s, char* base, uint64_t stride, int n, int tcap,
+                        int64_t max_pops, const RpCtx* ctx, const mxa_policy& p, double* obs, int32_t* flags, int64_t* a,
+                        double* act, double* state, int k, int first_zero) {
+  MxaStepPolicy pol{p, first_zero, a, act, state};
+  hipLaunchKernelGGL((mxa_step_policy_kernel<CFG, INSTR>), g, b, lds, s, base, stride, n, tcap, max_pops, ctx, pol, obs,
+                     flags, k);
+}
 #endif
 
 template <int CFG, bool GYM>
@@ -89,6 +97,8 @@ MxaEntry make_entry() {
     e.step_fast = launch_step<CFG, false>;
     e.step_many = launch_step_many<CFG, true>;
     e.step_many_fast = launch_step_many<CFG, false>;
+    e.step_policy = launch_step_policy<CFG, true>;
+    e.step_policy_fast = launch_step_policy<CFG, false>;
   }
 #endif
   return e;

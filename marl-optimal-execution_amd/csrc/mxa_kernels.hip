@@ -73,6 +73,8 @@
 #include "glibc_math.h"
 #include "mxa_layout.h"
 #include "mxa_config.h"
+#include "ddqn_device.h"
+#include "qnet_wave_device.h"
 
 
 typedef uint64_t u64;
@@ -4523,6 +4525,28 @@ struct Eng {
     if (U(R->rl_trade)) fail(ERR_RP_STOPPING);
   }
 
+  // mxa_rl_state_kernel's row (mxa_api.hip, include/mxa.h mxa_write_rl_state) from the live env
+  // state of a launch: the execution agent's record (in HBM between its events), the LDS replay
+  // header and the newest ABIDESEnvMetrics LOB
+  DEV void rl_state_row(double* o) {
+    auto R = rh();
+    const u64 rec = rec_fetch(PC.first_rl);
+    const u32 lo = (u32)rec, hi = (u32)(rec >> 32);
+    const i64 cash = (i64)(((u64)rdl(hi, AF_CASH >> 1) << 32) | rdl(lo, AF_CASH >> 1));
+    const i64 shares = (i64)(((u64)rdl(hi, AF_SHARES >> 1) << 32) | rdl(lo, AF_SHARES >> 1));
+    double v[MXA_RL_STATE_WORDS] = {(double)cash, (double)shares, (double)U(R->rl_exec), 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (U(R->m_cnt) > 0) {
+      const RpLob l = ring()[U(R->m_head)];
+      v[3] = (double)l.bid;
+      v[4] = (double)l.ask;
+      v[5] = (double)U(R->m_bq);
+      v[6] = (double)U(R->m_aq);
+      v[7] = (double)(l.flags & 3);
+    }
+    if (lane == 0)
+      for (int i = 0; i < MXA_RL_STATE_WORDS; i++) o[i] = v[i];
+  }
+
   // ---------------- TWAPExecutionAgent (agent/execution/baselines/twap_agent.py:9-63) on the
   // replay: ExecutionAgent.wakeup / receiveMessage / placeOrders (execution_agent.py:65-123).
   // The horizon is pd.date_range(rl_h0, ..., rl_hstep) (rl_nh times); RpHdr::rl_trade = -e.
@@ -6466,6 +6490,80 @@ __global__ __launch_bounds__(64, mxa_cfg::shape(CFG).waves) void mxa_step_kernel
   atomicAdd(&mxa::g_mxa_prof[64 + g.lane], (unsigned long long)g.prof[64 + g.lane]);
 #endif
 }
+
+// The closed-loop flavour (include/mxa.h mxa_step_policy): k_steps periods per launch as MANY, the
+// action of each step from the epsilon-greedy Q-network policy evaluated on the env's own wave
+// (qnet_wave_device.h; state_of / action_of of ddqn_device.h) on the observation the env's previous
+// step left, bit for bit the per-step sequence mxa_ddqn_state, mxa_qnet_act, mxa_step_device,
+// mxa_write_rl_state.  The step itself is mxa_step_kernel's loop body, restated here so that the
+// one-step and MANY kernels compile to the instructions they had; same LDS and launch bounds.
+struct MxaStepPolicy {
+  mxa_policy p;
+  int first_zero;    // step 0 of the launch places (0, 0, 0) without consulting the policy
+  int64_t* a;        // [k][n] action indices (-1: the zero step)
+  double* act;       // [k][n][3] action vectors
+  double* state;     // [k][n][MXA_RL_STATE_WORDS] mxa_rl_state_kernel's row after the step, or null
+};
+template <int CFG, bool INSTR>
+__global__ __launch_bounds__(64, mxa_cfg::shape(CFG).waves) void mxa_step_policy_kernel(
+    char* base, uint64_t stride, int n_envs, int trace_cap, int64_t max_pops, const RpCtx* ctx, MxaStepPolicy pol,
+    double* obs, int32_t* flags, int k_steps) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  int env = blockIdx.x;
+  if (env >= n_envs) return;
+  char* e = base + (size_t)env * stride;
+  mxa::Eng<CFG, false, false, INSTR> g(e, lds, trace_cap, ctx);
+  g.load();
+  const mxa_policy& p = pol.p;
+  for (int i = 0; i < k_steps; i++) {
+    const size_t row = (size_t)i * n_envs + env;
+    // choose_action + take_action (finished and errored envs too: the per-step path computes
+    // their rows from the sticky observation)
+    double a[3] = {0.0, 0.0, 0.0};
+    int64_t ai = -1;
+    if (!(pol.first_zero && i == 0)) {
+      auto R = g.rh();
+      const double o[2] = {R->obs[0], R->obs[1]};
+      float x[2];
+      state_of(o, p.grid0, p.n0, p.grid1, p.n1, p.nh, p.q0, x);
+      float q[qwave::kRegs] = {g.lane == 0 ? x[0] : g.lane == 1 ? x[1] : 0.f, 0.f, 0.f, 0.f};
+      qwave::forward(p.params, p.n_layers, p.dims, g.lane, q);
+      const int greedy = qwave::argmax(q, p.dims[p.n_layers]);
+      ai = qwave::select(greedy, p.test, p.enough, p.u, p.rnd, p.eps, row);
+      action_of(p.table + 3 * ai, o, p.q0, a);
+    }
+    if (g.lane == 0) {
+      pol.a[row] = ai;
+      for (int j = 0; j < 3; j++) pol.act[3 * row + j] = a[j];
+    }
+    if (g.status == ST_RUNNING) {
+      g.rl_place_orders(a);
+      g.end_step = 0;
+      g.run(max_pops);
+      if (g.status == ST_RUNNING) {  // after the loop: terminateRunner if the queue ran dry / past stop
+        u64 key;
+        u32 s;
+        if (g.q_peek(key, s) < 0 || g.cur > mxa::Eng<CFG>::PC.stop) g.status = ST_DONE;
+      }
+      if (g.status == ST_DONE) g.rp_terminate();
+    }
+    auto R = g.rh();
+    if (g.lane < 9) obs[9 * row + g.lane] = R->obs[g.lane];
+    u64 key;
+    u32 sq;
+    const bool pending = g.q_peek(key, sq) >= 0;  // all lanes: DPP reduction
+    // ABIDESEnv.step: done = not (queue non-empty and currentTime <= stopTime)
+    const int done = !(pending && g.cur <= mxa::Eng<CFG>::PC.stop) || g.status != ST_RUNNING;
+    const int hobs = mxa::U(R->has_obs);
+    if (g.lane == 0) flags[row] = done | (hobs ? 2 : 0) | (g.status == ST_ERROR ? 4 : 0);
+    if (pol.state != nullptr) g.rl_state_row(pol.state + (size_t)MXA_RL_STATE_WORDS * row);
+  }
+  g.save();
+#ifdef MXA_PROF
+  atomicAdd(&mxa::g_mxa_prof[g.lane], (unsigned long long)g.prof[g.lane]);
+  atomicAdd(&mxa::g_mxa_prof[64 + g.lane], (unsigned long long)g.prof[64 + g.lane]);
+#endif
+}
 #endif
 
 #ifdef MXA_API_TU  // (compiled once, in the C-ABI translation unit)
@@ -6498,5 +6596,33 @@ __global__ void mxa_math_probe_kernel(int mode, const double* x, const double* y
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   out[i] = mode == 0 ? gm_log(x[i]) : mode == 1 ? gm_exp(x[i]) : gm_pow(x[i], y[i]);
+}
+// the policy of mxa_step_policy_kernel on given input rows, one wave (block) per row: exactly the
+// device functions the step kernel calls (qnet_wave_device.h), for any dims[0] in 1..256
+struct MxaPolicyProbe {
+  const float* params;
+  int32_t n_layers, dims[qwave::kMaxLayers + 1];
+  int32_t test, enough;
+  const double* u;
+  const int64_t* rnd;
+  const double* eps;
+};
+__global__ __launch_bounds__(64) void mxa_policy_probe_kernel(MxaPolicyProbe p, int n, const float* x, float* q, int64_t* a) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  if (row >= n) return;
+  const int n_in = p.dims[0], n_out = p.dims[p.n_layers];
+  float act[qwave::kRegs];
+#pragma unroll
+  for (int r = 0; r < qwave::kRegs; r++) act[r] = 64 * r + lane < n_in ? x[(size_t)row * n_in + 64 * r + lane] : 0.f;
+  qwave::forward(p.params, p.n_layers, p.dims, lane, act);
+  if (q != nullptr) {
+#pragma unroll
+    for (int r = 0; r < qwave::kRegs; r++)
+      if (64 * r + lane < n_out) q[(size_t)row * n_out + 64 * r + lane] = act[r];
+  }
+  if (a == nullptr) return;
+  const int greedy = qwave::argmax(act, n_out);
+  const int64_t ai = qwave::select(greedy, p.test, p.enough, p.u, p.rnd, p.eps, (size_t)row);
+  if (lane == 0) a[row] = ai;
 }
 #endif

@@ -69,6 +69,14 @@ class AgentState(ctypes.Structure):
                 ("starting_cash", ctypes.c_int64)]
 
 
+class Policy(ctypes.Structure):  # mxa_policy: device pointers, host widths and scalars
+    _fields_ = [("params", ctypes.c_void_p), ("n_layers", ctypes.c_int32), ("dims", ctypes.c_int32 * 9),
+                ("grid0", ctypes.c_void_p), ("n0", ctypes.c_int32), ("grid1", ctypes.c_void_p), ("n1", ctypes.c_int32),
+                ("nh", ctypes.c_double), ("q0", ctypes.c_double), ("table", ctypes.c_void_p),
+                ("test", ctypes.c_int32), ("enough", ctypes.c_int32), ("u", ctypes.c_void_p), ("rnd", ctypes.c_void_p),
+                ("eps", ctypes.c_void_p)]
+
+
 class AgentFinal(ctypes.Structure):  # mxa_agent_final
     _fields_ = [("final_fundamental", ctypes.c_int64), ("valuation_int", ctypes.c_int64), ("valuation", ctypes.c_double),
                 ("kind", ctypes.c_int32), ("err", ctypes.c_int32)]
@@ -85,7 +93,7 @@ EXPORTS = ["mxa_create", "mxa_reset", "mxa_launch", "mxa_sync", "mxa_run", "mxa_
            "mxa_mm_defaults", "mxa_resident_envs", "mxa_set_exchange_log", "mxa_config_defaults",
            "mxa_config_compile", "mxa_config_key", "mxa_create_config", "mxa_config_info",
            "mxa_config_capacities",
-           "mxa_step_many", "mxa_set_launch_schedule"]
+           "mxa_step_many", "mxa_set_launch_schedule", "mxa_step_policy", "mxa_policy_probe"]
 COUNTER_WORDS = 34  # include/mxa.h MXA_COUNTER_WORDS
 INPLACE_WORDS = 4  # include/mxa.h MXA_INPLACE_WORDS
 RECORD_WORDS = 12  # include/mxa.h MXA_RECORD_WORDS
@@ -153,6 +161,9 @@ def load():
     L.mxa_step_device.argtypes = [P, P, P, P]
     if hasattr(L, "mxa_step_many"):  # (A/B builds of earlier sources lack it; tests check the exports)
         L.mxa_step_many.argtypes = [P, I32, P, P, P]
+    if hasattr(L, "mxa_step_policy"):  # (as mxa_step_many)
+        L.mxa_step_policy.argtypes = [P, I32, I32, ctypes.POINTER(Policy), P, P, P, P, P]
+        L.mxa_policy_probe.argtypes = [P, I32, P, P, I32, ctypes.POINTER(I32), I32, I32, P, P, P, P, P]
     L.mxa_finalize.argtypes = [P]
     L.mxa_read_final.argtypes = [P, I32, P, I32]
     if hasattr(L, "mxa_set_book_log"):

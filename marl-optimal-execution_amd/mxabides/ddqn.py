@@ -397,6 +397,39 @@ class DDQNLearner:
               obs_w, obs_p, tab_p, q0, out_a.data_ptr(), act_p, None)
         return out_a, out_act
 
+    def policy(self, task, test, enough, u, rnd):
+        """the mxa_policy POD (include/mxa.h) of the eval net as it stands, for
+        VecABIDESEnv.step_policy_device: the flat parameters and widths, `task`'s grid, action table,
+        horizon and quantity, epsilon, and choose_action's draws u / rnd ([k, n] float64 / int64
+        device tensors; None in test mode). The tensors it points to stay referenced by the returned
+        object, which the caller keeps until the launch is enqueued."""
+        from . import _lib
+        if not self.fused_act:
+            raise RuntimeError("DDQNLearner.policy needs fused_act (the in-kernel Q-values carry its bits)")
+        g0, g1 = (g.contiguous() for g in task.grid)
+        table = task.table.contiguous()
+        for name, t, dt in (("grid", g0, torch.float64), ("grid", g1, torch.float64), ("table", table, torch.float64)):
+            if t.dtype != dt or t.device != self.eflat.device:
+                raise ValueError("policy: task.%s must be a %s tensor on the learner's device" % (name, dt))
+        if table.dim() != 2 or table.shape[0] < self.n_actions or table.shape[1] != 3:
+            raise ValueError("policy: task.table must be a float64 [>= n_actions, 3] tensor")
+        if not test:
+            if u is None or rnd is None or u.dtype != torch.float64 or rnd.dtype != torch.int64 \
+                    or not u.is_contiguous() or not rnd.is_contiguous():
+                raise ValueError("policy: u / rnd must be contiguous float64 / int64 device tensors in train mode")
+        p = _lib.Policy()
+        p.params, p.n_layers = self.eflat.data_ptr(), len(self._qdims) - 1
+        for i, w in enumerate(self._qdims):
+            p.dims[i] = w
+        p.grid0, p.n0, p.grid1, p.n1 = g0.data_ptr(), g0.numel(), g1.data_ptr(), g1.numel()
+        p.nh, p.q0, p.table = float(task.nh), float(task.q0), table.data_ptr()
+        p.test, p.enough = int(bool(test)), int(bool(enough))
+        p.u = None if test else u.data_ptr()
+        p.rnd = None if test else rnd.data_ptr()
+        p.eps = self._eps.data_ptr()
+        p.keep = (self.eflat, g0, g1, table, u, rnd, self._eps)
+        return p
+
     def choose_action(self, s):
         """s [n, n_state] -> actions [n] int64 (epsilon-greedy per env in train mode)."""
         if self.fused_act:
@@ -687,8 +720,102 @@ def period_kernel(task, m, train, obs, st, prev, arrival, flags, alive, s, a, en
     return spare
 
 
+def rollout_chunks(nh=27, train_every=5, train=True):
+    """The launches of one closed-loop episode (run_episode(rollout=True)) as (first_zero, n_steps)
+    pairs: the episode is the zero step and the periods t = 0 .. nh-1, nh + 1 steps in all. When
+    training, a launch ends after every period t with t % train_every == 0, where the learner
+    updates the net the next period acts with; otherwise the episode is one launch. Only the first
+    launch holds the zero step."""
+    if not train:
+        return [(True, nh + 1)]
+    chunks, n = [], 1
+    for t in range(nh):
+        n += 1
+        if t % train_every == 0:
+            chunks.append((not chunks, n))
+            n = 0
+    if n:
+        chunks.append((not chunks, n))
+    return chunks
+
+
+def _run_rollout(env, learner, task, train_every, updates_per_train, record, timing):
+    """run_episode's loop with the policy inside the step kernel (include/mxa.h mxa_step_policy):
+    per launch the exploration draws of its periods, the launch, then period_kernel per period on
+    the recorded rows and the learner's update where run_episode's loop has it"""
+    from .gym import OBS_SIZE, RL_STATE_WORDS
+    dev, n, nh = learner.device, env.n_envs, task.nh
+    train, test = learner.mode == "train", learner.mode == "test"
+    K = nh + 1  # row 0: the zero step; row t + 1: period t
+    obs = torch.zeros((K, n, OBS_SIZE), dtype=torch.float64, device=dev)
+    flags = torch.zeros((K, n), dtype=torch.int32, device=dev)
+    st = torch.zeros((K, n, RL_STATE_WORDS), dtype=torch.float64, device=dev)
+    a_idx = torch.zeros((K, n), dtype=torch.int64, device=dev)
+    act = torch.zeros((K, n, 3), dtype=torch.float64, device=dev)
+    u = rnd = None
+    if not test:
+        u = torch.zeros((K, n), dtype=torch.float64, device=dev)
+        rnd = torch.zeros((K, n), dtype=torch.int64, device=dev)
+    rw = torch.zeros((nh, n), dtype=torch.float64, device=dev)
+    stored = torch.zeros((), dtype=torch.int64, device=dev)
+    ctx = {}
+
+    def launch(r0, k, first_zero, enough):
+        for r in range(r0 + (1 if first_zero else 0), r0 + k):  # _explore's draws, in its order
+            if not test:
+                u[r] = torch.rand(n, generator=learner.gen, device=dev, dtype=torch.float64)
+                rnd[r] = torch.randint(0, learner.n_actions, (n,), generator=learner.gen, device=dev)
+        pol = learner.policy(task, test, enough, None if test else u[r0:], None if test else rnd[r0:])
+        if timing is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        env.step_policy_device(k, pol, obs[r0].data_ptr(), flags[r0].data_ptr(), a_idx[r0].data_ptr(),
+                               act[r0].data_ptr(), st[r0].data_ptr(), first_zero=first_zero)
+        if timing is not None:
+            e1.record()
+            timing.append((e0, e1))
+        if record is not None:
+            record.extend(act[r].clone() for r in range(r0, r0 + k))
+        for r in range(r0, r0 + k):
+            if r == 0:  # after the zero step, as run_episode
+                ctx["alive"] = ((flags[0] & 2) != 0) & ((flags[0] & 5) == 0)
+                lob_ok = (st[0][:, 7] == 3)
+                ctx["arrival"] = torch.where(lob_ok, (st[0][:, 3] + st[0][:, 4]) / 2,
+                                             torch.ones_like(st[0][:, 3])).contiguous()
+                ctx["env_steps"] = ctx["alive"].to(torch.int64)
+                ctx["s"] = _state_device(task, obs[0], torch.empty((n, 2), dtype=torch.float32, device=dev))
+                ctx["spare"] = (torch.empty_like(ctx["s"]), torch.zeros_like(ctx["alive"]),
+                                torch.zeros((), dtype=torch.bool, device=dev))
+                continue
+            t = r - 1
+            s2, alive_next, live = period_kernel(task, learner.memory, train, obs[r], st[r], st[r - 1], ctx["arrival"],
+                                                 flags[r], ctx["alive"], ctx["s"], a_idx[r], ctx["env_steps"], stored,
+                                                 rw[t], ctx["spare"])
+            if train and t % train_every == 0:
+                for _ in range(updates_per_train):
+                    learner.learn(live=live)
+            ctx["s"], ctx["alive"], ctx["spare"] = s2, alive_next, (ctx["s"], ctx["alive"], live)
+
+    def enough_now():
+        return test or learner.memory.more_than(learner.batch_size - 1)
+
+    r0 = 0
+    for first_zero, k in rollout_chunks(nh, train_every, train):
+        end = r0 + k
+        # `enough` is one value per launch: until the replay holds a batch (it only grows), one
+        # step per launch, each period with choose_action's own test before it
+        while r0 < end:
+            enough = enough_now()
+            kk = end - r0 if enough else 1
+            launch(r0, kk, first_zero and r0 == 0, enough)
+            r0 += kk
+    return {"rewards": rw if nh else None, "actions": a_idx[1:].clone() if nh else None, "returns": rw.sum(0),
+            "flags": flags[K - 1], "arrival": ctx["arrival"], "stored": stored, "env_steps": ctx["env_steps"],
+            "steps": nh + 1}
+
+
 def run_episode(env, learner, task, seeds=None, train_every=5, updates_per_train=1, record=None, timing=None,
-                fused=None):
+                fused=None, rollout=None):
     """One episode of every env of a VecABIDESEnv (rmsc03 + DummyRL) driven by the learner, all on
     the current torch stream (the env must step on it: env.set_stream). Mirrors the agent's
     per-period loop (place_order, :275-299): observe, choose, act, then store the completed
@@ -704,11 +831,30 @@ def run_episode(env, learner, task, seeds=None, train_every=5, updates_per_train
 
     Returns a dict of device tensors (rewards [steps, n], actions [steps, n], flags) and the
     number of stored transitions. `record` (a list) receives the per-step action vectors;
-    `timing` (a list) receives a (start, end) torch.cuda.Event pair around every step launch."""
+    `timing` (a list) receives a (start, end) torch.cuda.Event pair around every step launch.
+
+    rollout: the policy inside the step kernel (include/mxa.h mxa_step_policy): the launches of
+    rollout_chunks, each running its periods of every env with the epsilon-greedy Q-network policy
+    evaluated in place, so an env does not wait for the slowest env of every step; the exploration
+    draws, period_kernel and the learner's updates are the same calls in the same order, and the
+    returned dict, the replay ring, the learner and the env blocks are bitwise those of
+    rollout=False. True needs the kernel path (fused not False), a CUDA learner with fused_act (the
+    in-kernel Q-values carry fused_act's bits) and both libraries, else RuntimeError; None (the
+    default) turns it on only where the environment has MXA_DDQN_ROLLOUT=1 and all of that holds.
+    Until the replay holds a batch (choose_action's `enough`), a launch runs one period."""
     from .gym import OBS_SIZE, RL_STATE_WORDS
     kernel = fused is not False and learner.device.type == "cuda" and lib() is not None
     if fused and not kernel:
         raise RuntimeError("run_episode(fused=True): libmxa_ddqn.so is not built (build_lib.build_ddqn)")
+    can_roll = kernel and learner.fused_act and hasattr(env.L, "mxa_step_policy")
+    if rollout and not can_roll:
+        raise RuntimeError("run_episode(rollout=True) needs the kernel path (fused not False), a CUDA learner with "
+                           "fused_act, libmxa_ddqn.so and a libmxa.so with mxa_step_policy")
+    if rollout is None:
+        rollout = os.environ.get("MXA_DDQN_ROLLOUT") == "1" and can_roll
+    if rollout:
+        env.reset(seeds=seeds)
+        return _run_rollout(env, learner, task, train_every, updates_per_train, record, timing)
     period = period_kernel if kernel else period_torch
     dev, n, nh = learner.device, env.n_envs, task.nh
     env.reset(seeds=seeds)
