@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -63,15 +64,15 @@ __global__ __launch_bounds__(1024) void mxa_compact_kernel(const char* base, uin
   if (threadIdx.x == 0) *count = done;
 }
 
-// Kernel.runner's stopTime of every env (EnvHdr::t_stop; 0 = the config's own)
-// the exchange-log switch of every env (EnvHdr::exlog)
-__global__ void mxa_set_exlog_kernel(char* base, uint64_t stride, int n, int32_t on) {
+// the handle's per-env header settings in every env: the exchange-log switch (EnvHdr::exlog) and
+// Kernel.runner's stopTime (EnvHdr::t_stop; 0 = the config's own).  No kernel changes either, so
+// an env holds the handle's values unless a build has just cleared its header
+__global__ void mxa_set_header_kernel(char* base, uint64_t stride, int n, int32_t exlog, int64_t t_stop) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) ((EnvHdr*)(base + (size_t)i * stride))->exlog = on;
-}
-__global__ void mxa_set_stop_kernel(char* base, uint64_t stride, int n, int64_t t_stop) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) ((EnvHdr*)(base + (size_t)i * stride))->t_stop = t_stop;
+  if (i >= n) return;
+  EnvHdr* h = (EnvHdr*)(base + (size_t)i * stride);
+  h->exlog = exlog;
+  h->t_stop = t_stop;
 }
 
 // the seeds of the episodes in progress (mxa_handle::d_built): a rebuilt env's (mask NULL: every
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(64) void mxa_records_kernel(const char* base, uint6
   const char* e = base + (size_t)i * stride;
   long long cash = 0, shares = 0, gain = 0;
   for (int a = a0 + lane; a < a1; a += 64) {
-    const uint32_t* r = (const uint32_t*)(e + off_ag + (size_t)a * 512);
+    const uint32_t* r = (const uint32_t*)(e + off_ag + (size_t)a * MXA_AGENT_BYTES);
     auto g64 = [&](int f) { return (long long)(((uint64_t)r[f + 1] << 32) | r[f]); };
     const long long c = g64(AF_CASH), s = g64(AF_SHARES);
     cash += c;
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(64) void mxa_counters_kernel(const char* base, uint
   const EnvHdr* h = (const EnvHdr*)e;
   long long w = 0;
   for (int a = lane; a < n_agents; a += 64)
-    w += (long long)(((const uint32_t*)(e + off_ag + (size_t)a * 512))[AF_RS_POS] - MXA_MT_N);
+    w += (long long)(((const uint32_t*)(e + off_ag + (size_t)a * MXA_AGENT_BYTES))[AF_RS_POS] - MXA_MT_N);
   for (int d = 32; d >= 1; d >>= 1) w += __shfl_xor(w, d, 64);
   int64_t* o = out + (size_t)MXA_COUNTER_WORDS * i;
   if (lane < 26) o[lane] = h->kc[lane];
@@ -191,40 +192,78 @@ __global__ void mxa_rl_state_kernel(const char* base, uint64_t stride, int n, ui
 
 }  // namespace
 
-struct mxa_handle {
+// device memory freed with its owner (the owner's device is current then: mxa_destroy, the probes)
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { free(); }
+  hipError_t alloc(size_t n) {
+    free();
+    return hipMalloc(&p, sizeof(T) * n);
+  }
+  void free() {
+    if (p) hipFree(p);
+    p = nullptr;
+  }
+  operator T*() const { return p; }
+};
+
+// host staging of a handle's device-resident arrays (the LOBSTER tape, the ExternalFileOracle
+// series): 256-byte-aligned pieces in one blob, each the RpCtx pointer `field` once uploaded
+struct TapeBlob {
+  std::vector<char> bytes;
+  std::vector<std::pair<const void**, size_t>> fields;  // (the RpCtx pointer, its piece's offset)
+  template <class T>
+  void add(const T*& field, const T* src, size_t n, size_t pad = 0) {
+    const size_t off = bytes.size();
+    fields.push_back({(const void**)&field, off});
+    bytes.resize((off + sizeof(T) * n + pad + 255) / 256 * 256, 0);
+    if (n) memcpy(bytes.data() + off, src, sizeof(T) * n);
+  }
+};
+
+// the handle's own stream and the timing events of its launches: the base, so that they are
+// destroyed after the members' device memory is freed (hipFree waits for the device's work)
+struct mxa_sync {
+  hipStream_t own = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~mxa_sync() {
+    if (ev0) hipEventDestroy(ev0);
+    if (ev1) hipEventDestroy(ev1);
+    if (own) hipStreamDestroy(own);
+  }
+};
+
+struct mxa_handle : mxa_sync {
   MxaParams P;
   int device = 0;
-  hipStream_t own = nullptr, stream = nullptr;
-  char* d_env = nullptr;
-  uint32_t* d_seeds = nullptr;  // the seeds the next mxa_reset builds from (mxa_set_seeds)
-  uint32_t* d_built = nullptr;  // the seed each env's current episode was built from (record word 5)
-  uint8_t* d_mask = nullptr;
-  int* d_count = nullptr;
-  int32_t* d_list = nullptr;  // [n_envs] the running envs after a launch (mxa_compact_kernel)
-  int64_t first_chunk = 0;    // mxa_set_launch_schedule: mxa_run's first launch (0: every launch `chunk`)
+  hipStream_t stream = nullptr;
+  DevBuf<char> d_env;
+  DevBuf<uint32_t> d_seeds;  // the seeds the next mxa_reset builds from (mxa_set_seeds)
+  DevBuf<uint32_t> d_built;  // the seed each env's current episode was built from (record word 5)
+  DevBuf<uint8_t> d_mask;
+  DevBuf<int> d_count;
+  DevBuf<int32_t> d_list;   // [n_envs] the running envs after a launch (mxa_compact_kernel)
+  int64_t first_chunk = 0;  // mxa_set_launch_schedule: mxa_run's first launch (0: every launch `chunk`)
+  MxaEntry e{};             // the configuration's launchers (mxa_entry.h)
   size_t lds = 0;
-  mxa_build_fn build = nullptr;
-  mxa_inplace_fn inplace = nullptr;                // in-place group counts of the configuration (mxa_read_inplace)
-  mxa_run_fn run = nullptr, run_log = nullptr;     // run_log: with the book-update log
-  mxa_run_fn run_fast = nullptr;                   // hash off, no trace ring: instrumentation compiled out
-  mxa_step_fn step = nullptr, step_fast = nullptr;  // GymKernel handles (replay, rmsc03_rl)
-  mxa_step_many_fn step_many = nullptr, step_many_fast = nullptr;  // k steps per launch
-  mxa_step_policy_fn step_policy = nullptr, step_policy_fast = nullptr;  // k periods per launch, policy in place
-  mxa_stop_fn stop = nullptr, stop_log = nullptr;  // kernelStopping pass (plain Kernel.runner configs)
-  mxa_agent_final* d_final = nullptr;
-  BlRec* d_blog = nullptr;  // book-update log [n_envs][blog_cap] (mxa_set_book_log)
+  DevBuf<mxa_agent_final> d_final;
+  DevBuf<BlRec> d_blog;  // book-update log [n_envs][blog_cap] (mxa_set_book_log)
   int32_t blog_cap = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_ms = 0;
   std::string err;
   // GymKernel handles (ABIDESEnv replay, rmsc03 + DummyRL): stepped with actions
   bool gym = false;
   bool replay = false;  // the replay ladder book + tape
-  RpCtx ctx{};             // host copy (pointers are device pointers)
-  RpCtx* d_ctx = nullptr;
-  char* d_tape = nullptr;
-  double *d_act = nullptr, *d_obs = nullptr;
-  int32_t* d_flags = nullptr;
+  RpCtx ctx{};          // host copy (pointers are device pointers)
+  DevBuf<RpCtx> d_ctx;
+  TapeBlob tape;  // uploaded to d_tape by create_common
+  DevBuf<char> d_tape;
+  DevBuf<double> d_act, d_obs;
+  DevBuf<int32_t> d_flags;
   bool parity_hash = true;  // per-pop trace hash (test instrumentation); off: kernel tcap -1
   // GymKernel handles: mxa_reset continues Order.order_id / Order._order_ids of the previous
   // episode (one process running consecutive ABIDESEnv episodes)
@@ -233,20 +272,16 @@ struct mxa_handle {
   bool started = false;  // a launch ran since the last whole-handle mxa_reset (the exchange log is fixed then)
   int64_t t_stop = 0;  // mxa_set_stop_time: Kernel.runner's stopTime override (0: the config's)
   int32_t tcap_arg() const { return (parity_hash || P.L.trace_cap > 0) ? P.L.trace_cap : -1; }
-  // the run kernel of the current settings: the log variant, the instrumented one, or (hash off,
-  // no trace ring) the one without the parity instrumentation
-  mxa_run_fn run_kernel() const {
-    if (d_blog) return run_log;
-    return (tcap_arg() < 0 && run_fast) ? run_fast : run;
+  // a launcher of the current settings: the instrumented one or, with the hash off and no trace
+  // ring, the one without the parity instrumentation where the configuration has it
+  template <class F>
+  F pick(F instr, F fast) const {
+    return tcap_arg() < 0 && fast ? fast : instr;
   }
-  std::vector<char> tape_blob;  // host staging of the tape (uploaded by create_common)
-  size_t tb_t, tb_oid, tb_dense, tb_price, tb_size, tb_buy, tb_tm, tb_tm0, tb_uid, tb_ufirst;
-  bool ext = false;  // ExternalFileOracle configurations: the fundamental series in d_tape
-  size_t tb_fs_t = 0, tb_fs_v = 0;
+  mxa_run_fn run_kernel() const { return d_blog ? e.run_log : pick(e.run, e.run_fast); }
   // MXA_RMSC03_MM: per-env market-maker options (config/rmsc03.py --mm-*), read by every build
   std::vector<MmParams> mm;
-  MmParams* d_mmp = nullptr;
-  mxa_occ_fn occ = nullptr;  // resident waves per CU of the handle's measured kernel
+  DevBuf<MmParams> d_mmp;
 };
 
 static int hip_fail(mxa_handle* h, hipError_t e, const char* what) {
@@ -258,54 +293,120 @@ static int hip_fail(mxa_handle* h, hipError_t e, const char* what) {
     hipError_t _e = (x);                             \
     if (_e != hipSuccess) return hip_fail(h, _e, #x); \
   } while (0)
+// every entry point that works on a handle's device starts here: the caller's current device may differ
+#define ENTER(h) HIPCHK(h, hipSetDevice(h->device))
 
-static int create_common(mxa_handle* h, int32_t n_envs, const uint32_t* seeds, int32_t device, mxa_handle** out);
+// pops a step launch may take: a step ends at its own time (GymKernel.stepRunner), never at this
+static constexpr int64_t STEP_POPS = (int64_t)1 << 40;
 
 // the configuration's launchers (mxa_entry.h); false: not built into this library
-static bool bind(mxa_handle* h, int cfg) {
-  MxaEntry e{};
+static bool builtin_entry(int cfg, MxaEntry& e) {
   switch (cfg) {
+#define MXA_ENTRY_CASE(id) \
+  case id: e = MXA_ENTRY_FN(id)(); return true;
 #ifdef MXA_ONLY_RMSC03
-  case MXA_ONLY_CFG: e = MXA_ENTRY_CAT(mxa_entry_, MXA_ONLY_CFG)(); break;
+    MXA_ENTRY_CASE(MXA_ONLY_CFG)
 #else
-  case 0: e = mxa_entry_0(); break;
-  case 1: e = mxa_entry_1(); break;
-  case 2: e = mxa_entry_2(); break;
-  case 3: e = mxa_entry_3(); break;
-  case 4: e = mxa_entry_4(); break;
-  case 5: e = mxa_entry_5(); break;
-  case 6: e = mxa_entry_6(); break;
-  case 7: e = mxa_entry_7(); break;
-  case 8: e = mxa_entry_8(); break;
-  case 9: e = mxa_entry_9(); break;
-  case 10: e = mxa_entry_10(); break;
-  case 11: e = mxa_entry_11(); break;
-  case 12: e = mxa_entry_12(); break;
-  case 13: e = mxa_entry_13(); break;
-  case 14: e = mxa_entry_14(); break;
-  case 15: e = mxa_entry_15(); break;
-  case 16: e = mxa_entry_16(); break;
-  case 17: e = mxa_entry_17(); break;
+    MXA_CONFIGS(MXA_ENTRY_CASE)
 #endif
-  default: return false;
   }
-  h->build = e.build;
-  h->inplace = e.inplace;
-  h->run = e.run;
-  h->run_log = e.run_log;
-  h->run_fast = e.run_fast;
-  h->stop = e.stop;
-  h->stop_log = e.stop_log;
-  h->step = e.step;
-  h->step_fast = e.step_fast;
-  h->step_many = e.step_many;
-  h->step_many_fast = e.step_many_fast;
-  h->step_policy = e.step_policy;
-  h->step_policy_fast = e.step_policy_fast;
+  return false;
+}
+
+// the one constructor: a handle bound to launchers `e` with the parameter block P sized for
+// (n_envs, trace_cap).  Owned, so a constructor's early return needs no clean-up
+static std::unique_ptr<mxa_handle> new_handle(const MxaEntry& e, size_t lds, const MxaParams& P, int32_t n_envs,
+                                              int32_t trace_cap) {
+  auto h = std::make_unique<mxa_handle>();
+  h->e = e;
+  h->lds = lds;
+  h->P = P;
+  h->P.n_envs = n_envs;
+  h->P.L.trace_cap = trace_cap;
+  h->P.L.env_stride = mxa_cfg::align_up(P.L.off_trace + (uint64_t)trace_cap * MXA_TRACE_ROW_BYTES, 256);
+  return h;
+}
+// of a built-in configuration (GymKernel handles: those with a step kernel); null: not in this library
+static std::unique_ptr<mxa_handle> new_handle(int cfg, int32_t n_envs, int32_t trace_cap) {
+  MxaEntry e{};
+  if (!builtin_entry(cfg, e)) return nullptr;
+  auto h = new_handle(e, mxa_cfg::lds_bytes(cfg), mxa_cfg::params(cfg), n_envs, trace_cap);
   h->gym = e.step != nullptr;
-  h->occ = e.occ;
-  h->lds = mxa_cfg::lds_bytes(cfg);
-  return true;
+  return h;
+}
+
+// the device side of every constructor.  *out takes the handle first: a HIP failure leaves it with
+// the caller, who reads mxa_last_error and destroys it
+static int create_common(std::unique_ptr<mxa_handle> owned, const uint32_t* seeds, int32_t device, mxa_handle** out) {
+  mxa_handle* h = *out = owned.release();
+  const int n_envs = h->P.n_envs;
+  h->device = device;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
+  HIPCHK(h, hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
+  h->stream = h->own;
+  HIPCHK(h, hipEventCreate(&h->ev0));
+  HIPCHK(h, hipEventCreate(&h->ev1));
+  size_t bytes = (size_t)h->P.L.env_stride * n_envs;
+  HIPCHK(h, h->d_env.alloc(bytes));
+  HIPCHK(h, h->d_seeds.alloc(n_envs));
+  HIPCHK(h, h->d_built.alloc(n_envs));
+  HIPCHK(h, h->d_mask.alloc(n_envs));
+  HIPCHK(h, h->d_count.alloc(1));
+  HIPCHK(h, h->d_list.alloc(n_envs));
+  HIPCHK(h, hipMemsetAsync(h->d_env, 0, bytes, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, sizeof(uint32_t) * n_envs, hipMemcpyHostToDevice, h->stream));
+  const TapeBlob& tape = h->tape;
+  if (!tape.bytes.empty()) {
+    HIPCHK(h, h->d_tape.alloc(tape.bytes.size()));
+    HIPCHK(h, hipMemcpyAsync(h->d_tape, tape.bytes.data(), tape.bytes.size(), hipMemcpyHostToDevice, h->stream));
+    for (auto& [field, off] : tape.fields) *field = h->d_tape + off;
+  }
+  if (!h->mm.empty()) {
+    HIPCHK(h, h->d_mmp.alloc(n_envs));
+    HIPCHK(h, hipMemcpyAsync(h->d_mmp, h->mm.data(), sizeof(MmParams) * n_envs, hipMemcpyHostToDevice, h->stream));
+    h->ctx.mmp = h->d_mmp;
+  }
+  if (h->gym || !tape.bytes.empty() || !h->mm.empty()) {
+    HIPCHK(h, h->d_ctx.alloc(1));
+    HIPCHK(h, hipMemcpyAsync(h->d_ctx, &h->ctx, sizeof(RpCtx), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, h->d_act.alloc(3 * (size_t)n_envs));
+    HIPCHK(h, h->d_obs.alloc(9 * (size_t)n_envs));
+    HIPCHK(h, h->d_flags.alloc(n_envs));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  const int rc = mxa_reset(h, nullptr);  // a fresh process: ids from 0
+  h->persist_ids = h->gym;               // later resets continue the process (Order.py:8-9)
+  return rc;
+}
+
+// one launch between the handle's timing events (mxa_last_kernel_ms reads their distance)
+template <class Launch>
+static int timed_launch(mxa_handle* h, Launch launch) {
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch();
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  return MXA_OK;
+}
+
+// a step launch of a GymKernel handle: the arguments every step launcher starts with, then `tail`
+template <class F, class... Tail>
+static int step_launch(mxa_handle* h, F instr, F fast, Tail... tail) {
+  ENTER(h);
+  return timed_launch(h, [&] {
+    h->pick(instr, fast)(dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, h->P.n_envs,
+                         h->tcap_arg(), STEP_POPS, h->d_ctx, tail...);
+  });
+}
+
+// the handle's header settings into every env (after a build cleared headers, or a new setting)
+static int set_headers(mxa_handle* h) {
+  const int n = h->P.n_envs;
+  hipLaunchKernelGGL(mxa_set_header_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_env, h->P.L.env_stride,
+                     n, h->exlog, h->t_stop);
+  HIPCHK(h, hipGetLastError());
+  return MXA_OK;
 }
 
 extern "C" {
@@ -323,7 +424,6 @@ int mxa_prof_read(uint64_t* out64) {
 int mxa_create(int32_t config, int32_t n_envs, const uint32_t* seeds, int32_t device, int32_t trace_cap,
                mxa_handle** out) {
   if (!out || n_envs <= 0 || !seeds || trace_cap < 0) return MXA_EINVAL;
-  mxa_handle* h = new mxa_handle();
   static_assert((int)MXA_RMSC03 == (int)MXA_CFG_RMSC03 && (int)MXA_SPARSE_ZI_100 == (int)MXA_CFG_SPARSE_ZI_100 &&
                     (int)MXA_SPARSE_ZI_1000 == (int)MXA_CFG_SPARSE_ZI_1000 &&
                     (int)MXA_MARKETREPLAY == (int)MXA_CFG_MARKETREPLAY && (int)MXA_RMSC03_RL == (int)MXA_CFG_RMSC03_RL &&
@@ -344,27 +444,20 @@ int mxa_create(int32_t config, int32_t n_envs, const uint32_t* seeds, int32_t de
                     offsetof(MmParams, wake_up_freq) && offsetof(mxa_mm_params, mm_num_ticks) == offsetof(MmParams, num_ticks),
                 "mxa_mm_params is MmParams");
   if (config == MXA_RMSC03_MM) {  // the config script's defaults in every env
-    std::vector<mxa_mm_params> d(n_envs > 0 ? n_envs : 0);
-    for (auto& x : d) x = mxa_mm_defaults();
-    delete h;
+    std::vector<mxa_mm_params> d(n_envs, mxa_mm_defaults());
     return mxa_create_params(MXA_RMSC03, n_envs, seeds, d.data(), device, trace_cap, out);
   }
   // replay handles: mxa_create_replay(_runner); ExternalFileOracle configurations: mxa_create_hist
   if (config == MXA_MARKETREPLAY || config == MXA_MARKETREPLAY_RUNNER || config == MXA_MARKETREPLAY_TWAP ||
-      config == MXA_HIST_FUND_VALUE ||
-      config == MXA_HIST_FUND_DIVERSE || !bind(h, config)) {
-    delete h;
+      config == MXA_HIST_FUND_VALUE || config == MXA_HIST_FUND_DIVERSE)
     return MXA_EINVAL;
-  }
-  h->P = mxa_cfg::params(config);
-  h->P.n_envs = n_envs;
-  h->P.L.trace_cap = trace_cap;
-  h->P.L.env_stride = mxa_cfg::env_stride(config, trace_cap);
+  auto h = new_handle(config, n_envs, trace_cap);
+  if (!h) return MXA_EINVAL;
   if (h->gym) {  // the DummyRL metrics header + deque after the trace (no ladder, no tape)
     h->ctx.L = mxa_cfg::replay_layout(h->P.L.env_stride, 0, 0, 0, 0, 0, 0, 0);
     h->P.L.env_stride = h->ctx.L.end;
   }
-  return create_common(h, n_envs, seeds, device, out);
+  return create_common(std::move(h), seeds, device, out);
 }
 
 static int check_mm(const mxa_mm_params* p, int n) {
@@ -397,23 +490,16 @@ int mxa_create_params(int32_t config, int32_t n_envs, const uint32_t* seeds, con
                       int32_t device, int32_t trace_cap, mxa_handle** out) {
   if (!out || n_envs <= 0 || !seeds || !per_env || trace_cap < 0 || config != MXA_RMSC03) return MXA_EINVAL;
   if (check_mm(per_env, n_envs)) return MXA_EINVAL;
-  mxa_handle* h = new mxa_handle();
-  if (!bind(h, MXA_CFG_RMSC03_MM)) {
-    delete h;
-    return MXA_EINVAL;
-  }
-  h->P = mxa_cfg::params(MXA_CFG_RMSC03_MM);
-  h->P.n_envs = n_envs;
-  h->P.L.trace_cap = trace_cap;
-  h->P.L.env_stride = mxa_cfg::env_stride(MXA_CFG_RMSC03_MM, trace_cap);
+  auto h = new_handle(MXA_CFG_RMSC03_MM, n_envs, trace_cap);
+  if (!h) return MXA_EINVAL;
   h->mm.assign((const MmParams*)per_env, (const MmParams*)per_env + n_envs);
-  return create_common(h, n_envs, seeds, device, out);
+  return create_common(std::move(h), seeds, device, out);
 }
 
 int mxa_set_mm_params(mxa_handle* h, const mxa_mm_params* per_env) {
   if (!h || !per_env || !h->d_mmp) return MXA_EINVAL;
   if (check_mm(per_env, h->P.n_envs)) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
+  ENTER(h);
   memcpy(h->mm.data(), per_env, sizeof(MmParams) * h->P.n_envs);
   HIPCHK(h, hipMemcpyAsync(h->d_mmp, h->mm.data(), sizeof(MmParams) * h->P.n_envs, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -421,12 +507,13 @@ int mxa_set_mm_params(mxa_handle* h, const mxa_mm_params* per_env) {
 }
 
 int mxa_resident_envs(const mxa_handle* h) {
-  if (!h || !h->occ) return MXA_EINVAL;
+  if (!h || !h->e.occ) return MXA_EINVAL;
   int dev = 0, cus = 0;
+  // (a const handle: ENTER's error text has nowhere to go)
   if (hipSetDevice(h->device) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return MXA_EHIP;
-  const int per_cu = h->occ(h->lds);
+  const int per_cu = h->e.occ(h->lds);
   if (per_cu < 0) return MXA_EHIP;
   return per_cu * cus < h->P.n_envs ? per_cu * cus : h->P.n_envs;
 }
@@ -440,24 +527,12 @@ int mxa_create_hist(int32_t config, int32_t n_envs, const uint32_t* seeds, int32
   for (int i = 0; i < n_fund; i++)
     if ((i && fund_t[i] < fund_t[i - 1]) || !(fund_v[i] == fund_v[i]) || fund_v[i] > 1e15 || fund_v[i] < -1e15)
       return MXA_EINVAL;  // unsorted times or a value int(round()) cannot take (NaN raises in the reference)
-  mxa_handle* h = new mxa_handle();
-  if (!bind(h, config)) {
-    delete h;
-    return MXA_EINVAL;
-  }
-  h->P = mxa_cfg::params(config);
-  h->P.n_envs = n_envs;
-  h->P.L.trace_cap = trace_cap;
-  h->P.L.env_stride = mxa_cfg::env_stride(config, trace_cap);
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  h->tb_fs_t = 0;
-  h->tb_fs_v = al(8ull * n_fund);
-  h->tape_blob.assign(al(h->tb_fs_v + 8ull * n_fund), 0);
-  memcpy(h->tape_blob.data() + h->tb_fs_t, fund_t, 8ull * n_fund);
-  memcpy(h->tape_blob.data() + h->tb_fs_v, fund_v, 8ull * n_fund);
+  auto h = new_handle(config, n_envs, trace_cap);
+  if (!h) return MXA_EINVAL;
+  h->tape.add(h->ctx.fs_t, fund_t, n_fund);
+  h->tape.add(h->ctx.fs_v, fund_v, n_fund);
   h->ctx.fs_n = n_fund;
-  h->ext = true;
-  return create_common(h, n_envs, seeds, device, out);
+  return create_common(std::move(h), seeds, device, out);
 }
 
 // ---- runtime compositions (include/mxa.h mxa_config): one specialised library per composition
@@ -637,24 +712,8 @@ int mxa_create_config(const mxa_config* cfg, int32_t n_envs, const uint32_t* see
     return cfg_fail("mxa_create_config: " + so + " was built by another libmxa");
   c.date_ns = cfg->date_ns;
   if (memcmp(&c, cfg, sizeof c) != 0) return cfg_fail("mxa_create_config: " + so + " holds another composition");
-  mxa_handle* h = new mxa_handle();
-  h->build = e.build;
-  h->inplace = e.inplace;
-  h->run = e.run;
-  h->run_log = e.run_log;
-  h->run_fast = e.run_fast;
-  h->stop = e.stop;
-  h->stop_log = e.stop_log;
-  h->step = e.step;
-  h->step_fast = e.step_fast;
-  h->gym = false;
-  h->occ = e.occ;
-  h->lds = lds;
-  h->P = P;
-  h->P.n_envs = n_envs;
-  h->P.L.trace_cap = trace_cap;
-  h->P.L.env_stride = mxa_cfg::align_up(P.L.off_trace + (uint64_t)trace_cap * MXA_TRACE_WORDS * 8, 256);
-  return create_common(h, n_envs, seeds, device, out);
+  // a plain Kernel.runner handle whatever the entry holds: compositions are no GymKernel handles
+  return create_common(new_handle(e, lds, P, n_envs, trace_cap), seeds, device, out);
 }
 
 int mxa_config_info(int32_t config, int64_t* out8) {
@@ -670,65 +729,6 @@ int mxa_config_info(int32_t config, int64_t* out8) {
   out8[6] = P.start;
   out8[7] = P.stop;
   return MXA_OK;
-}
-
-static int create_common(mxa_handle* h, int32_t n_envs, const uint32_t* seeds, int32_t device, mxa_handle** out) {
-  h->device = device;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) {
-    *out = h;
-    return hip_fail(h, e, "hipSetDevice");
-  }
-  *out = h;
-  HIPCHK(h, hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
-  h->stream = h->own;
-  HIPCHK(h, hipEventCreate(&h->ev0));
-  HIPCHK(h, hipEventCreate(&h->ev1));
-  size_t bytes = (size_t)h->P.L.env_stride * n_envs;
-  HIPCHK(h, hipMalloc(&h->d_env, bytes));
-  HIPCHK(h, hipMalloc(&h->d_seeds, sizeof(uint32_t) * n_envs));
-  HIPCHK(h, hipMalloc(&h->d_built, sizeof(uint32_t) * n_envs));
-  HIPCHK(h, hipMalloc(&h->d_mask, n_envs));
-  HIPCHK(h, hipMalloc(&h->d_count, sizeof(int)));
-  HIPCHK(h, hipMalloc(&h->d_list, sizeof(int32_t) * (size_t)std::max(1, h->P.n_envs)));
-  HIPCHK(h, hipMemsetAsync(h->d_env, 0, bytes, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, sizeof(uint32_t) * n_envs, hipMemcpyHostToDevice, h->stream));
-  if (h->replay) {
-    HIPCHK(h, hipMalloc(&h->d_tape, h->tape_blob.size()));
-    HIPCHK(h, hipMemcpyAsync(h->d_tape, h->tape_blob.data(), h->tape_blob.size(), hipMemcpyHostToDevice, h->stream));
-    h->ctx.t = (const int64_t*)(h->d_tape + h->tb_t);
-    h->ctx.oid = (const int32_t*)(h->d_tape + h->tb_oid);
-    h->ctx.dense = (const int32_t*)(h->d_tape + h->tb_dense);
-    h->ctx.price = (const int32_t*)(h->d_tape + h->tb_price);
-    h->ctx.size = (const int32_t*)(h->d_tape + h->tb_size);
-    h->ctx.buy = (const int8_t*)(h->d_tape + h->tb_buy);
-    h->ctx.tm = (const int64_t*)(h->d_tape + h->tb_tm);
-    h->ctx.tm0 = (const int32_t*)(h->d_tape + h->tb_tm0);
-    h->ctx.uid = (const int32_t*)(h->d_tape + h->tb_uid);
-    h->ctx.ufirst = (const int32_t*)(h->d_tape + h->tb_ufirst);
-  }
-  if (h->ext) {
-    HIPCHK(h, hipMalloc(&h->d_tape, h->tape_blob.size()));
-    HIPCHK(h, hipMemcpyAsync(h->d_tape, h->tape_blob.data(), h->tape_blob.size(), hipMemcpyHostToDevice, h->stream));
-    h->ctx.fs_t = (const int64_t*)(h->d_tape + h->tb_fs_t);
-    h->ctx.fs_v = (const double*)(h->d_tape + h->tb_fs_v);
-  }
-  if (!h->mm.empty()) {
-    HIPCHK(h, hipMalloc(&h->d_mmp, sizeof(MmParams) * n_envs));
-    HIPCHK(h, hipMemcpyAsync(h->d_mmp, h->mm.data(), sizeof(MmParams) * n_envs, hipMemcpyHostToDevice, h->stream));
-    h->ctx.mmp = h->d_mmp;
-  }
-  if (h->gym || h->ext || h->replay || !h->mm.empty()) {
-    HIPCHK(h, hipMalloc(&h->d_ctx, sizeof(RpCtx)));
-    HIPCHK(h, hipMemcpyAsync(h->d_ctx, &h->ctx, sizeof(RpCtx), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMalloc(&h->d_act, sizeof(double) * 3 * n_envs));
-    HIPCHK(h, hipMalloc(&h->d_obs, sizeof(double) * 9 * n_envs));
-    HIPCHK(h, hipMalloc(&h->d_flags, sizeof(int32_t) * n_envs));
-  }
-  if (h->gym || h->ext || h->replay || !h->mm.empty()) HIPCHK(h, hipStreamSynchronize(h->stream));
-  const int rc = mxa_reset(h, nullptr);  // a fresh process: ids from 0
-  h->persist_ids = h->gym;               // later resets continue the process (Order.py:8-9)
-  return rc;
 }
 
 // ABIDESEnv on a LOBSTER tape (agent_config.py / ABIDESEnv.py), or config/marketreplay.py under
@@ -786,15 +786,9 @@ static int create_replay(int cfg, const int64_t* t, const int64_t* oid, const in
              return a.first == b.first;
            }),
            uf.end());  // sorted by (id, record): the first of each id is kept
-  mxa_handle* h = new mxa_handle();
-  if (!bind(h, cfg)) {
-    delete h;
-    return MXA_EINVAL;
-  }
+  auto h = new_handle(cfg, n_envs, trace_cap);
+  if (!h) return MXA_EINVAL;
   h->replay = true;
-  h->P = P0;
-  h->P.n_envs = n_envs;
-  h->P.L.trace_cap = trace_cap;
   // dense order-id index in first-appearance order; distinct times and their first records
   std::vector<int32_t> dense(n_rec), tm0;
   std::vector<int64_t> tm;
@@ -822,53 +816,33 @@ static int create_replay(int cfg, const int64_t* t, const int64_t* oid, const in
   const int C = n_rec + h->P.rl_ids;  // every placement could rest at once
   // auto-id dense range: the episode's auto ids, the explicit ids they may skip over in a later
   // episode (MXA_AUTO_SKIP), and one never-present index (orders.get(0) without an auto id 0)
-  h->ctx.L = mxa_cfg::replay_layout(mxa_cfg::env_stride(cfg, trace_cap), (int)pmin, (int)(pmax - pmin + 1), C,
-                                    n_ids, (int)auto_cap + MXA_AUTO_SKIP + 1, ntm, n_rec);
+  h->ctx.L = mxa_cfg::replay_layout(h->P.L.env_stride, (int)pmin, (int)(pmax - pmin + 1), C, n_ids,
+                                    (int)auto_cap + MXA_AUTO_SKIP + 1, ntm, n_rec);
   h->ctx.nuid = (int32_t)uf.size();
   h->ctx.twap_trade = twap_trade;
   h->ctx.umin = uf.empty() ? INT32_MAX : uf[0].first;
   h->P.L.env_stride = h->ctx.L.end;
-  // tape blob: t, oid, dense, price, size, buy, tm, tm0 (256-B aligned pieces)
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  size_t off = 0;
-  h->tb_t = off;
-  off = al(off + 8ull * n_rec);
-  h->tb_oid = off;
-  off = al(off + 4ull * n_rec);
-  h->tb_dense = off;
-  off = al(off + 4ull * n_rec);
-  h->tb_price = off;
-  off = al(off + 4ull * n_rec);
-  h->tb_size = off;
-  off = al(off + 4ull * n_rec);
-  h->tb_buy = off;
-  off = al(off + n_rec);
-  h->tb_tm = off;
-  off = al(off + 8ull * ntm);
-  h->tb_tm0 = off;
-  off = al(off + 4ull * (ntm + 1));
-  h->tb_uid = off;
-  off = al(off + 4ull * uf.size() + 4);
-  h->tb_ufirst = off;
-  off = al(off + 4ull * uf.size() + 4);
-  h->tape_blob.assign(off, 0);
-  char* b = h->tape_blob.data();
-  for (int i = 0; i < n_rec; i++) {
-    ((int64_t*)(b + h->tb_t))[i] = t[i];
-    ((int32_t*)(b + h->tb_oid))[i] = (int32_t)oid[i];
-    ((int32_t*)(b + h->tb_dense))[i] = dense[i];
-    ((int32_t*)(b + h->tb_price))[i] = (int32_t)price[i];
-    ((int32_t*)(b + h->tb_size))[i] = (int32_t)size[i];
-    ((int8_t*)(b + h->tb_buy))[i] = buy[i] ? 1 : 0;
+  // the tape in the device's word sizes, then the blob in this order
+  std::vector<int32_t> oid32(oid, oid + n_rec), price32(price, price + n_rec), size32(size, size + n_rec), uid, ufirst;
+  std::vector<int8_t> buy8(n_rec);
+  for (int i = 0; i < n_rec; i++) buy8[i] = buy[i] ? 1 : 0;
+  for (auto& u : uf) {
+    uid.push_back(u.first);
+    ufirst.push_back(u.second);
   }
-  memcpy(b + h->tb_tm, tm.data(), 8ull * ntm);
-  memcpy(b + h->tb_tm0, tm0.data(), 4ull * (ntm + 1));
-  for (size_t i = 0; i < uf.size(); i++) {
-    ((int32_t*)(b + h->tb_uid))[i] = uf[i].first;
-    ((int32_t*)(b + h->tb_ufirst))[i] = uf[i].second;
-  }
+  RpCtx& c = h->ctx;
+  h->tape.add(c.t, t, n_rec);
+  h->tape.add(c.oid, oid32.data(), n_rec);
+  h->tape.add(c.dense, dense.data(), n_rec);
+  h->tape.add(c.price, price32.data(), n_rec);
+  h->tape.add(c.size, size32.data(), n_rec);
+  h->tape.add(c.buy, buy8.data(), n_rec);
+  h->tape.add(c.tm, tm.data(), ntm);
+  h->tape.add(c.tm0, tm0.data(), ntm + 1);
+  h->tape.add(c.uid, uid.data(), uid.size(), 4);  // (one spare word each: the pieces are never empty)
+  h->tape.add(c.ufirst, ufirst.data(), ufirst.size(), 4);
   std::vector<uint32_t> seeds(n_envs, 0u);  // nothing in this composition draws
-  return create_common(h, n_envs, seeds.data(), device, out);
+  return create_common(std::move(h), seeds.data(), device, out);
 #endif
 }
 
@@ -878,7 +852,7 @@ int mxa_step(mxa_handle* h, const double* actions, double* obs, int32_t* flags) 
 #ifdef MXA_NO_GYM
   return MXA_EINVAL;
 #else
-  HIPCHK(h, hipSetDevice(h->device));
+  ENTER(h);
   int n = h->P.n_envs;
   HIPCHK(h, hipMemcpyAsync(h->d_act, actions, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
   int rc = mxa_step_device(h, h->d_act, h->d_obs, h->d_flags);
@@ -899,14 +873,7 @@ int mxa_step_many(mxa_handle* h, int32_t k, const double* d_actions, double* d_o
 #ifdef MXA_NO_GYM
   return MXA_EINVAL;
 #else
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  (h->tcap_arg() < 0 && h->step_many_fast ? h->step_many_fast : h->step_many)(
-      dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, h->P.n_envs, h->tcap_arg(),
-      (int64_t)1 << 40, (const RpCtx*)h->d_ctx, d_actions, d_obs, d_flags, k);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  return MXA_OK;
+  return step_launch(h, h->e.step_many, h->e.step_many_fast, d_actions, d_obs, d_flags, (int)k);
 #endif
 }
 
@@ -922,15 +889,9 @@ int mxa_step_policy(mxa_handle* h, int32_t k, int32_t first_zero, const mxa_poli
 #ifdef MXA_NO_GYM
   return MXA_EINVAL;
 #else
-  if (!h->step_policy) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  (h->tcap_arg() < 0 && h->step_policy_fast ? h->step_policy_fast : h->step_policy)(
-      dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, h->P.n_envs, h->tcap_arg(),
-      (int64_t)1 << 40, (const RpCtx*)h->d_ctx, *p, d_obs, d_flags, d_a, d_act, d_state, k, first_zero != 0);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  return MXA_OK;
+  if (!h->e.step_policy) return MXA_EINVAL;
+  return step_launch(h, h->e.step_policy, h->e.step_policy_fast, *p, d_obs, d_flags, d_a, d_act, d_state, (int)k,
+                     (int)(first_zero != 0));
 #endif
 }
 
@@ -940,64 +901,42 @@ int mxa_step_device(mxa_handle* h, const double* d_actions, double* d_obs, int32
 #ifdef MXA_NO_GYM
   return MXA_EINVAL;
 #else
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  (h->tcap_arg() < 0 && h->step_fast ? h->step_fast : h->step)(dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env,
-                                                                 h->P.L.env_stride, h->P.n_envs, h->tcap_arg(),
-          (int64_t)1 << 40, (const RpCtx*)h->d_ctx, d_actions, d_obs, d_flags);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  return MXA_OK;
+  return step_launch(h, h->e.step, h->e.step_fast, d_actions, d_obs, d_flags);
 #endif
 }
 
 int mxa_reset(mxa_handle* h, const uint8_t* mask) {
   if (!h) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
+  ENTER(h);
+  const int n = h->P.n_envs;
   const uint8_t* dm = nullptr;
-  if (h->persist_ids) {  // mask value 2: rebuild the env, keep its order-id counters
-    std::vector<uint8_t> m2(h->P.n_envs);
-    for (int i = 0; i < h->P.n_envs; i++) m2[i] = (!mask || mask[i]) ? 2 : 0;
-    HIPCHK(h, hipMemcpyAsync(h->d_mask, m2.data(), h->P.n_envs, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // m2 is a host temporary
-    dm = h->d_mask;
-  } else if (mask) {
-    std::vector<uint8_t> m1(h->P.n_envs);
-    for (int i = 0; i < h->P.n_envs; i++) m1[i] = mask[i] ? 1 : 0;
-    HIPCHK(h, hipMemcpyAsync(h->d_mask, m1.data(), h->P.n_envs, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (mask || h->persist_ids) {
+    // 1: rebuild the env; 2 (persist_ids): rebuild it and keep its order-id counters
+    const uint8_t on = h->persist_ids ? 2 : 1;
+    std::vector<uint8_t> m(n);
+    for (int i = 0; i < n; i++) m[i] = (!mask || mask[i]) ? on : 0;
+    HIPCHK(h, hipMemcpyAsync(h->d_mask, m.data(), n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // m is a host temporary
     dm = h->d_mask;
   }
-  h->build(dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, h->P.n_envs, h->d_seeds, dm,
-           h->d_ctx);
+  h->e.build(dim3(n), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, n, h->d_seeds, dm, h->d_ctx);
   HIPCHK(h, hipGetLastError());
-  hipLaunchKernelGGL(mxa_built_seeds_kernel, dim3((h->P.n_envs + 255) / 256), dim3(256), 0, h->stream, h->d_built,
-                     h->d_seeds, dm, h->P.n_envs);
+  hipLaunchKernelGGL(mxa_built_seeds_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_built, h->d_seeds,
+                     dm, n);
   HIPCHK(h, hipGetLastError());
   if (!mask) h->started = false;
-  if (h->exlog) {  // the build cleared the header: the switch outlives resets
-    const int n = h->P.n_envs;
-    hipLaunchKernelGGL(mxa_set_exlog_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_env,
-                       h->P.L.env_stride, n, h->exlog);
-    HIPCHK(h, hipGetLastError());
-  }
-  if (h->t_stop > 0) {  // the build cleared the header: the override outlives resets
-    const int n = h->P.n_envs;
-    hipLaunchKernelGGL(mxa_set_stop_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_env,
-                       h->P.L.env_stride, n, h->t_stop);
-    HIPCHK(h, hipGetLastError());
-  }
+  // the build cleared the header: the exchange-log switch and the stopTime override outlive resets
+  if (h->exlog || h->t_stop > 0)
+    if (int rc = set_headers(h)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MXA_OK;
 }
 
 int mxa_set_stop_time(mxa_handle* h, int64_t t_stop_ns) {
   if (!h || h->gym) return MXA_EINVAL;  // GymKernel handles: ABIDESEnv's own stop (ABIDESEnv.py:42-46)
-  HIPCHK(h, hipSetDevice(h->device));
+  ENTER(h);
   h->t_stop = t_stop_ns > 0 ? t_stop_ns : 0;
-  const int n = h->P.n_envs;
-  hipLaunchKernelGGL(mxa_set_stop_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_env, h->P.L.env_stride,
-                     n, h->t_stop);
-  HIPCHK(h, hipGetLastError());
+  if (int rc = set_headers(h)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MXA_OK;
 }
@@ -1024,7 +963,7 @@ int mxa_set_id_persistence(mxa_handle* h, int32_t on) {
 
 int mxa_launch(mxa_handle* h, int64_t max_pops) {
   if (!h || h->gym) return MXA_EINVAL;  // GymKernel handles advance by mxa_step
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   h->started = true;
   h->run_kernel()(dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, h->P.n_envs, h->tcap_arg(), max_pops,
          h->d_ctx, h->d_blog, h->blog_cap, nullptr);
@@ -1034,14 +973,14 @@ int mxa_launch(mxa_handle* h, int64_t max_pops) {
 
 int mxa_sync(mxa_handle* h) {
   if (!h) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MXA_OK;
 }
 
 int mxa_run(mxa_handle* h, int64_t chunk, int32_t max_launches, int32_t* launches_out) {
   if (!h || chunk <= 0 || h->gym) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
+  ENTER(h);
   int launches = 0;
   float total = 0;
   h->started = true;
@@ -1065,11 +1004,11 @@ int mxa_run(mxa_handle* h, int64_t chunk, int32_t max_launches, int32_t* launche
   while (running > 0) {
     if (max_launches > 0 && launches >= max_launches) break;
     // one wave per running env: every env (no list) while none has finished
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    h->run_kernel()(dim3(running), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, n, h->tcap_arg(), pops,
-                    h->d_ctx, h->d_blog, h->blog_cap, running == n ? nullptr : h->d_list);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    rc = timed_launch(h, [&] {
+      h->run_kernel()(dim3(running), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, n, h->tcap_arg(), pops,
+                      h->d_ctx, h->d_blog, h->blog_cap, running == n ? nullptr : (const int32_t*)h->d_list);
+    });
+    if (rc != MXA_OK) return rc;
     launches++;
     if ((rc = compact(running)) != MXA_OK) return rc;
     float ms = 0;
@@ -1092,14 +1031,13 @@ int mxa_set_launch_schedule(mxa_handle* h, int64_t first_chunk) {
 // `cap` records per env in one device buffer; every env's record count restarts at 0
 int mxa_set_book_log(mxa_handle* h, int32_t cap) {
   // Kernel.runner handles, the replay's (config/marketreplay.py) included; not GymKernel handles
-  if (!h || h->gym || !h->run_log || cap < 0) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
+  if (!h || h->gym || !h->e.run_log || cap < 0) return MXA_EINVAL;
+  ENTER(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->d_blog) HIPCHK(h, hipFree(h->d_blog));
-  h->d_blog = nullptr;
+  h->d_blog.free();
   h->blog_cap = 0;
   if (cap > 0) {
-    HIPCHK(h, hipMalloc(&h->d_blog, sizeof(BlRec) * (size_t)cap * h->P.n_envs));
+    HIPCHK(h, h->d_blog.alloc((size_t)cap * h->P.n_envs));
     h->blog_cap = cap;
   }
   HIPCHK(h, hipMemset2DAsync(h->d_env + offsetof(EnvHdr, blog_n), h->P.L.env_stride, 0, sizeof(int32_t), h->P.n_envs,
@@ -1113,7 +1051,7 @@ int mxa_set_book_log(mxa_handle* h, int32_t cap) {
 // the exchange's own log (ExchangeAgent.log -> EXCHANGE_AGENT.bz2) in the book-update log: the
 // log-variant kernels write its records (mxa_layout.h BL_EV_*) while EnvHdr::exlog is set
 int mxa_set_exchange_log(mxa_handle* h, int32_t on) {
-  if (!h || h->gym || !h->run_log || on < 0 || on > 1) return MXA_EINVAL;
+  if (!h || h->gym || !h->e.run_log || on < 0 || on > 1) return MXA_EINVAL;
   if (on && !h->d_blog) return MXA_EINVAL;  // it rides in the book-update log: mxa_set_book_log first
   if (h->started && on != h->exlog) {
     // placements logged before the switch would be missing from the log (its order rows name
@@ -1121,12 +1059,9 @@ int mxa_set_exchange_log(mxa_handle* h, int32_t on) {
     h->err = "mxa_set_exchange_log: set it before the first launch (or after a whole-handle mxa_reset)";
     return MXA_EINVAL;
   }
-  HIPCHK(h, hipSetDevice(h->device));
+  ENTER(h);
   h->exlog = on;
-  const int n = h->P.n_envs;
-  hipLaunchKernelGGL(mxa_set_exlog_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_env, h->P.L.env_stride,
-                     n, on);
-  HIPCHK(h, hipGetLastError());
+  if (int rc = set_headers(h)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MXA_OK;
 }
@@ -1139,7 +1074,7 @@ int mxa_read_book_log(mxa_handle* h, int32_t env, mxa_book_rec* out, int64_t cap
   static_assert((int)MXA_BL_EV_RX == (int)BL_EV_RX && (int)MXA_BL_EV_NT == (int)BL_EV_NT &&
                     (int)MXA_BL_EV_PLACE == (int)BL_EV_PLACE && (int)MXA_BL_EV_END == (int)BL_EV_END,
                 "exchange-log record codes");
-  HIPCHK(h, hipSetDevice(h->device));
+  ENTER(h);
   EnvHdr hd;
   HIPCHK(h, hipMemcpyAsync(&hd, h->d_env + (size_t)env * h->P.L.env_stride, sizeof(hd), hipMemcpyDeviceToHost,
                            h->stream));
@@ -1157,12 +1092,12 @@ int mxa_read_book_log(mxa_handle* h, int32_t env, mxa_book_rec* out, int64_t cap
 }
 
 int mxa_finalize(mxa_handle* h) {
-  if (!h || h->gym || !h->stop) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
+  if (!h || h->gym || !h->e.stop) return MXA_EINVAL;
+  ENTER(h);
   const size_t rows = (size_t)h->P.n_envs * h->P.n_agents;
-  if (!h->d_final) HIPCHK(h, hipMalloc(&h->d_final, rows * sizeof(mxa_agent_final)));
-  (h->d_blog ? h->stop_log : h->stop)(dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, h->P.n_envs, h->d_final,
-          h->d_blog, h->blog_cap, h->d_ctx);
+  if (!h->d_final) HIPCHK(h, h->d_final.alloc(rows));
+  (h->d_blog ? h->e.stop_log : h->e.stop)(dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride,
+                                          h->P.n_envs, h->d_final, h->d_blog, h->blog_cap, h->d_ctx);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MXA_OK;
@@ -1170,7 +1105,7 @@ int mxa_finalize(mxa_handle* h) {
 
 int mxa_read_final(mxa_handle* h, int32_t env, mxa_agent_final* out, int32_t cap) {
   if (!h || !h->d_final || env < 0 || env >= h->P.n_envs || !out || cap < h->P.n_agents) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   HIPCHK(h, hipMemcpyAsync(out, h->d_final + (size_t)env * h->P.n_agents, sizeof(mxa_agent_final) * h->P.n_agents,
                            hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1179,7 +1114,7 @@ int mxa_read_final(mxa_handle* h, int32_t env, mxa_agent_final* out, int32_t cap
 
 int mxa_read_summary(mxa_handle* h, mxa_env_summary* out) {
   if (!h || !out) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   int n = h->P.n_envs;
   std::vector<EnvHdr> hd(n);
   HIPCHK(h, hipMemcpy2DAsync(hd.data(), sizeof(EnvHdr), h->d_env, h->P.L.env_stride, sizeof(EnvHdr), n,
@@ -1201,13 +1136,13 @@ int mxa_read_summary(mxa_handle* h, mxa_env_summary* out) {
 
 int mxa_read_agents(mxa_handle* h, int32_t env, mxa_agent_state* out, int32_t cap) {
   if (!h || env < 0 || env >= h->P.n_envs) return MXA_ERANGE;
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   int n = std::min(cap, h->P.n_agents);
-  std::vector<uint32_t> rec((size_t)h->P.n_agents * 128);
+  std::vector<uint32_t> rec((size_t)h->P.n_agents * MXA_AGENT_WORDS);
   HIPCHK(h, hipMemcpy(rec.data(), h->d_env + (size_t)env * h->P.L.env_stride + h->P.L.off_ag, rec.size() * 4,
                       hipMemcpyDeviceToHost));
   for (int a = 0; a < n; a++) {
-    const uint32_t* r = &rec[(size_t)a * 128];
+    const uint32_t* r = &rec[(size_t)a * MXA_AGENT_WORDS];
     auto g64 = [&](int f) { return (int64_t)(((uint64_t)r[f + 1] << 32) | r[f]); };
     out[a].cash = g64(AF_CASH);
     out[a].shares = g64(AF_SHARES);
@@ -1230,7 +1165,7 @@ int mxa_read_agents(mxa_handle* h, int32_t env, mxa_agent_state* out, int32_t ca
 
 int mxa_read_book(mxa_handle* h, int32_t env, int32_t side, int64_t* out4, int32_t cap) {
   if (!h || env < 0 || env >= h->P.n_envs) return MXA_ERANGE;
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   if (h->replay) {  // price ladder: levels best-first, FIFO lists
     const RpLayout& L = h->ctx.L;
     char* e = h->d_env + (size_t)env * h->P.L.env_stride;
@@ -1278,19 +1213,19 @@ int mxa_read_book(mxa_handle* h, int32_t env, int32_t side, int64_t* out4, int32
 
 int mxa_read_trace(mxa_handle* h, int32_t env, int64_t* out, int64_t cap, int64_t* nout) {
   if (!h || env < 0 || env >= h->P.n_envs) return MXA_ERANGE;
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   EnvHdr hd;
   char* e = h->d_env + (size_t)env * h->P.L.env_stride;
   HIPCHK(h, hipMemcpy(&hd, e, sizeof hd, hipMemcpyDeviceToHost));
   int64_t n = std::min<int64_t>(std::min<int64_t>(hd.trace_len, h->P.L.trace_cap), cap);
-  if (n > 0) HIPCHK(h, hipMemcpy(out, e + h->P.L.off_trace, (size_t)n * 80, hipMemcpyDeviceToHost));
+  if (n > 0) HIPCHK(h, hipMemcpy(out, e + h->P.L.off_trace, (size_t)n * MXA_TRACE_ROW_BYTES, hipMemcpyDeviceToHost));
   if (nout) *nout = n;
   return MXA_OK;
 }
 
 int mxa_set_seeds(mxa_handle* h, const uint32_t* seeds) {
   if (!h || !seeds) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, sizeof(uint32_t) * h->P.n_envs, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MXA_OK;
@@ -1298,7 +1233,7 @@ int mxa_set_seeds(mxa_handle* h, const uint32_t* seeds) {
 
 int mxa_write_results(mxa_handle* h, void* device_out) {
   if (!h || !device_out) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   int n = h->P.n_envs;
   hipLaunchKernelGGL(mxa_results_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_env, h->P.L.env_stride,
                      n, (int64_t*)device_out);
@@ -1308,7 +1243,7 @@ int mxa_write_results(mxa_handle* h, void* device_out) {
 
 int mxa_write_records(mxa_handle* h, void* device_out) {
   if (!h || !device_out) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
+  ENTER(h);
   int n = h->P.n_envs;
   // GymKernel handles: the execution agent; Kernel.runner handles: every trading agent
   const int a0 = h->gym ? h->P.first_rl : 1, a1 = h->gym ? h->P.first_rl + 1 : h->P.n_agents;
@@ -1320,7 +1255,7 @@ int mxa_write_records(mxa_handle* h, void* device_out) {
 
 int mxa_read_counters(mxa_handle* h, int64_t* out) {
   if (!h || !out) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
+  ENTER(h);
   const int n = h->P.n_envs;
   int64_t* d = nullptr;
   HIPCHK(h, hipMallocAsync((void**)&d, sizeof(int64_t) * MXA_COUNTER_WORDS * n, h->stream));
@@ -1334,10 +1269,10 @@ int mxa_read_counters(mxa_handle* h, int64_t* out) {
 }
 
 int mxa_read_inplace(mxa_handle* h, uint64_t* out) {
-  if (!h || !out || !h->inplace) return MXA_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
+  if (!h || !out || !h->e.inplace) return MXA_EINVAL;
+  ENTER(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  return h->inplace(out) ? MXA_EHIP : MXA_OK;
+  return h->e.inplace(out) ? MXA_EHIP : MXA_OK;
 }
 
 int mxa_set_parity_hash(mxa_handle* h, int32_t enabled) {
@@ -1348,10 +1283,11 @@ int mxa_set_parity_hash(mxa_handle* h, int32_t enabled) {
 
 int mxa_write_rl_state(mxa_handle* h, double* device_out) {
   if (!h || !device_out || !h->gym || h->P.n_rl != 1) return MXA_EINVAL;
+  ENTER(h);
   int n = h->P.n_envs;
   hipLaunchKernelGGL(mxa_rl_state_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_env, h->P.L.env_stride,
-                     n, (uint32_t)(h->P.L.off_ag + 512u * (uint32_t)h->P.first_rl), h->ctx.L.off_rh, h->ctx.L.off_ring,
-                     device_out);
+                     n, (uint32_t)(h->P.L.off_ag + (uint32_t)MXA_AGENT_BYTES * (uint32_t)h->P.first_rl), h->ctx.L.off_rh,
+                     h->ctx.L.off_ring, device_out);
   HIPCHK(h, hipGetLastError());
   return MXA_OK;
 }
@@ -1359,7 +1295,7 @@ int mxa_write_rl_state(mxa_handle* h, double* device_out) {
 int mxa_read_raw(mxa_handle* h, int32_t env, int64_t offset, int64_t bytes, void* out) {
   if (!h || env < 0 || env >= h->P.n_envs || offset < 0 || bytes < 0 || offset + bytes > (int64_t)h->P.L.env_stride)
     return MXA_ERANGE;
-  HIPCHK(h, hipSetDevice(h->device));  // the caller's current device may differ
+  ENTER(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(out, h->d_env + (size_t)env * h->P.L.env_stride + offset, bytes, hipMemcpyDeviceToHost));
   return MXA_OK;
@@ -1389,56 +1325,32 @@ const char* mxa_build_id(void) { return MXA_BUILD_ID; }
 void mxa_destroy(mxa_handle* h) {
   if (!h) return;
   hipSetDevice(h->device);
-  if (h->d_env) hipFree(h->d_env);
-  if (h->d_seeds) hipFree(h->d_seeds);
-  if (h->d_built) hipFree(h->d_built);
-  if (h->d_mask) hipFree(h->d_mask);
-  if (h->d_count) hipFree(h->d_count);
-  if (h->d_list) hipFree(h->d_list);
-  if (h->d_tape) hipFree(h->d_tape);
-  if (h->d_ctx) hipFree(h->d_ctx);
-  if (h->d_mmp) hipFree(h->d_mmp);
-  if (h->d_act) hipFree(h->d_act);
-  if (h->d_obs) hipFree(h->d_obs);
-  if (h->d_flags) hipFree(h->d_flags);
-  if (h->d_final) hipFree(h->d_final);
-  if (h->d_blog) hipFree(h->d_blog);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
-  if (h->own) hipStreamDestroy(h->own);
-  delete h;
+  delete h;  // its device memory, then its events and stream
 }
 
 int mxa_rng_probe(int32_t device, uint32_t seed, int32_t mode, double a, double b, int32_t n, double* out) {
-  if (n <= 0 || !out) return MXA_EINVAL;
+  if (n <= 0 || !out || mode < 0 || mode > 5) return MXA_EINVAL;
   if (hipSetDevice(device) != hipSuccess) return MXA_EHIP;
-  double* d_out = nullptr;
-  uint32_t* d_s = nullptr;
-  if (mode < 0 || mode > 5) return MXA_EINVAL;
-  if (hipMalloc(&d_out, sizeof(double) * n) != hipSuccess) return MXA_ENOMEM;
-  if (hipMalloc(&d_s, MXA_RNG_WORDS * 4) != hipSuccess) return MXA_ENOMEM;
-  hipLaunchKernelGGL(mxa_rng_probe_kernel, dim3(1), dim3(64), 0, 0, seed, mode, a, b, n, d_out, d_s);
-  hipError_t e = hipMemcpy(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost);
-  hipFree(d_out);
-  hipFree(d_s);
-  return e == hipSuccess ? MXA_OK : MXA_EHIP;
+  DevBuf<double> d_out;
+  DevBuf<uint32_t> d_s;
+  if (d_out.alloc(n) != hipSuccess || d_s.alloc(MXA_RNG_WORDS) != hipSuccess) return MXA_ENOMEM;
+  hipLaunchKernelGGL(mxa_rng_probe_kernel, dim3(1), dim3(64), 0, 0, seed, mode, a, b, n, d_out.p, d_s.p);
+  if (hipGetLastError() != hipSuccess) return MXA_EHIP;
+  return hipMemcpy(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost) == hipSuccess ? MXA_OK : MXA_EHIP;
 }
 
 int mxa_math_probe(int32_t device, int32_t mode, const double* x, const double* y, double* out, int64_t n) {
   if (n <= 0 || !x || !out) return MXA_EINVAL;
   if (hipSetDevice(device) != hipSuccess) return MXA_EHIP;
-  double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+  DevBuf<double> dx, dy, dout;
   size_t bytes = sizeof(double) * n;
-  if (hipMalloc(&dx, bytes) != hipSuccess || hipMalloc(&dy, bytes) != hipSuccess || hipMalloc(&dout, bytes) != hipSuccess)
-    return MXA_ENOMEM;
+  if (dx.alloc(n) != hipSuccess || dy.alloc(n) != hipSuccess || dout.alloc(n) != hipSuccess) return MXA_ENOMEM;
   hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
   hipMemcpy(dy, y ? y : x, bytes, hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(mxa_math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, mode, dx, dy, dout, n);
-  hipError_t e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
-  hipFree(dx);
-  hipFree(dy);
-  hipFree(dout);
-  return e == hipSuccess ? MXA_OK : MXA_EHIP;
+  hipLaunchKernelGGL(mxa_math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, mode, dx.p, dy.p, dout.p,
+                     n);
+  if (hipGetLastError() != hipSuccess) return MXA_EHIP;
+  return hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost) == hipSuccess ? MXA_OK : MXA_EHIP;
 }
 
 int mxa_policy_probe(void* stream, int32_t n, const float* x, const float* params, int32_t n_layers, const int32_t* dims,

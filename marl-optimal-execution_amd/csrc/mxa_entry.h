@@ -41,22 +41,14 @@ struct MxaEntry {
   mxa_occ_fn occ;              // hipOccupancyMaxActiveBlocksPerMultiprocessor of run_fast / step_fast
 };
 
-MxaEntry mxa_entry_0();
-MxaEntry mxa_entry_1();
-MxaEntry mxa_entry_2();
-MxaEntry mxa_entry_3();
-MxaEntry mxa_entry_4();
-MxaEntry mxa_entry_5();
-MxaEntry mxa_entry_6();
-MxaEntry mxa_entry_7();
-MxaEntry mxa_entry_8();
-MxaEntry mxa_entry_9();
-MxaEntry mxa_entry_10();
-MxaEntry mxa_entry_11();
-MxaEntry mxa_entry_12();
-MxaEntry mxa_entry_13();
-MxaEntry mxa_entry_14();
-MxaEntry mxa_entry_15();
-MxaEntry mxa_entry_16();
-MxaEntry mxa_entry_17();
-#define MXA_N_CONFIGS 18
+// the built-in configurations (mxa_layout.h mxa_config_id): the one list behind the declarations
+// below, MXA_N_CONFIGS and the C-ABI's switch.  A new configuration is one more X(<id>) here
+#define MXA_CONFIGS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17)
+
+#define MXA_ENTRY_CAT2(a, b) a##b
+#define MXA_ENTRY_CAT(a, b) MXA_ENTRY_CAT2(a, b)
+#define MXA_ENTRY_FN(id) MXA_ENTRY_CAT(mxa_entry_, id)  // mxa_entry_<id>; id may be a macro
+#define MXA_ENTRY_DECL(id) MxaEntry MXA_ENTRY_FN(id)();
+MXA_CONFIGS(MXA_ENTRY_DECL)
+#define MXA_ENTRY_COUNT(id) +1
+#define MXA_N_CONFIGS (0 MXA_CONFIGS(MXA_ENTRY_COUNT))

@@ -123,7 +123,5 @@ extern "C" __attribute__((visibility("default"))) int mxa_custom_entry(MxaEntry*
   return (int)sizeof(MxaParams);
 }
 #else
-#define MXA_ENTRY_CAT2(a, b) a##b
-#define MXA_ENTRY_CAT(a, b) MXA_ENTRY_CAT2(a, b)
-MxaEntry MXA_ENTRY_CAT(mxa_entry_, MXA_INST_CFG)() { return make_entry<MXA_INST_CFG>(); }
+MxaEntry MXA_ENTRY_FN(MXA_INST_CFG)() { return make_entry<MXA_INST_CFG>(); }
 #endif

@@ -307,6 +307,8 @@ typedef struct {
 } Layout;
 
 // agent record: 128 dwords (512 B); lane i of the owning wave holds dwords 2i, 2i+1
+#define MXA_AGENT_WORDS 128
+#define MXA_AGENT_BYTES (MXA_AGENT_WORDS * 4)
 enum {
   AF_TYPE = 0, AF_FLAGS = 1, AF_STATE = 2, AF_NORD = 3,
   AF_MKT_OPEN = 4, AF_MKT_CLOSE = 6, AF_CASH = 8, AF_SHARES = 10, AF_LAST_TRADE = 12,
@@ -332,7 +334,7 @@ enum {
   AF_NUSED = 117,     // open-order list slots used (live + tombstones); AF_NORD = live
   AF_ATIME = 120,     // Kernel.agentCurrentTimes[a]
   AF_COMP = 122,      // Kernel.agentComputationDelays[a]
-  AF_END = 128
+  AF_END = MXA_AGENT_WORDS
 };
 // AF_FLAGS bits
 enum {
@@ -403,3 +405,4 @@ typedef struct {
 } MxaParams;
 
 #define MXA_TRACE_WORDS 10
+#define MXA_TRACE_ROW_BYTES (MXA_TRACE_WORDS * 8)  // one trace row: MXA_TRACE_WORDS int64

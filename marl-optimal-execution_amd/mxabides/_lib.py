@@ -82,18 +82,75 @@ class AgentFinal(ctypes.Structure):  # mxa_agent_final
                 ("kind", ctypes.c_int32), ("err", ctypes.c_int32)]
 
 
-EXPORTS = ["mxa_create", "mxa_reset", "mxa_launch", "mxa_sync", "mxa_run", "mxa_read_summary", "mxa_read_agents",
-           "mxa_read_book", "mxa_read_trace", "mxa_n_agents", "mxa_n_envs", "mxa_env_bytes", "mxa_set_stream",
-           "mxa_last_kernel_ms", "mxa_last_error", "mxa_destroy", "mxa_rng_probe", "mxa_math_probe",
-           "mxa_set_seeds", "mxa_write_results", "mxa_read_raw", "mxa_layout", "mxa_create_replay", "mxa_step",
-           "mxa_step_device", "mxa_finalize", "mxa_read_final", "mxa_write_rl_state", "mxa_set_parity_hash",
-           "mxa_build_id", "mxa_set_book_log", "mxa_read_book_log", "mxa_write_records", "mxa_set_id_persistence",
-           "mxa_read_counters", "mxa_read_inplace", "mxa_create_hist", "mxa_create_replay_runner",
-           "mxa_set_stop_time", "mxa_run_until", "mxa_create_replay_twap", "mxa_create_params", "mxa_set_mm_params",
-           "mxa_mm_defaults", "mxa_resident_envs", "mxa_set_exchange_log", "mxa_config_defaults",
-           "mxa_config_compile", "mxa_config_key", "mxa_create_config", "mxa_config_info",
-           "mxa_config_capacities",
-           "mxa_step_many", "mxa_set_launch_schedule", "mxa_step_policy", "mxa_policy_probe"]
+class MmParams(ctypes.Structure):  # mxa_mm_params (mxabides.configs.MM_PARAMS_DTYPE is its numpy twin)
+    _fields_ = [("mm_pov", ctypes.c_double), ("mm_min_order_size", ctypes.c_int32), ("mm_window_size", ctypes.c_int32),
+                ("mm_num_ticks", ctypes.c_int32), ("pad", ctypes.c_int32), ("mm_wake_up_freq_ns", ctypes.c_int64)]
+
+
+_P, _I32, _I64, _U32, _D, _S = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_double,
+                                ctypes.c_char_p)
+_OUT, _N32, _N64 = ctypes.POINTER(_P), ctypes.POINTER(_I32), ctypes.POINTER(_I64)  # mxa_handle**, int32_t*, int64_t*
+_TAPE = [_P, _P, _P, _P, _P, _I32]  # t, oid, price, size, buy, n_rec
+# every export of include/mxa.h: name -> (argtypes, restype)
+BINDINGS = {
+    "mxa_create": ([_I32, _I32, _P, _I32, _I32, _OUT], _I32),
+    "mxa_create_hist": ([_I32, _I32, _P, _I32, _I32, _P, _P, _I32, _OUT], _I32),
+    "mxa_mm_defaults": ([], MmParams),
+    "mxa_create_params": ([_I32, _I32, _P, _P, _I32, _I32, _OUT], _I32),
+    "mxa_config_defaults": ([_I32, _P], _I32),
+    "mxa_config_compile": ([_P, _S, _P, _I32], _I32),
+    "mxa_config_key": ([_P, _P], _I32),
+    "mxa_config_capacities": ([_P, _P], _I32),
+    "mxa_create_config": ([_P, _I32, _P, _I32, _I32, _S, _OUT], _I32),
+    "mxa_config_info": ([_I32, _P], _I32),
+    "mxa_set_mm_params": ([_P, _P], _I32),
+    "mxa_resident_envs": ([_P], _I32),
+    "mxa_reset": ([_P, _P], _I32),
+    "mxa_set_id_persistence": ([_P, _I32], _I32),
+    "mxa_launch": ([_P, _I64], _I32),
+    "mxa_sync": ([_P], _I32),
+    "mxa_run": ([_P, _I64, _I32, _N32], _I32),
+    "mxa_set_launch_schedule": ([_P, _I64], _I32),
+    "mxa_set_stop_time": ([_P, _I64], _I32),
+    "mxa_run_until": ([_P, _I64, _P], _I32),
+    "mxa_finalize": ([_P], _I32),
+    "mxa_read_final": ([_P, _I32, _P, _I32], _I32),
+    "mxa_read_summary": ([_P, _P], _I32),
+    "mxa_read_agents": ([_P, _I32, _P, _I32], _I32),
+    "mxa_read_book": ([_P, _I32, _I32, _P, _I32], _I32),
+    "mxa_read_trace": ([_P, _I32, _P, _I64, _N64], _I32),
+    "mxa_set_seeds": ([_P, _P], _I32),
+    "mxa_write_results": ([_P, _P], _I32),
+    "mxa_write_records": ([_P, _P], _I32),
+    "mxa_read_counters": ([_P, _P], _I32),
+    "mxa_read_inplace": ([_P, _P], _I32),
+    "mxa_read_raw": ([_P, _I32, _I64, _I64, _P], _I32),
+    "mxa_layout": ([_P, _P], _I32),
+    "mxa_n_agents": ([_P], _I32),
+    "mxa_n_envs": ([_P], _I32),
+    "mxa_env_bytes": ([_P], _I64),
+    "mxa_set_stream": ([_P, _P], _I32),
+    "mxa_last_kernel_ms": ([_P], _D),
+    "mxa_last_error": ([_P], _S),
+    "mxa_destroy": ([_P], None),
+    "mxa_create_replay": (_TAPE + [_I32, _I32, _I32, _OUT], _I32),
+    "mxa_create_replay_runner": (_TAPE + [_I32, _I32, _I32, _OUT], _I32),
+    "mxa_create_replay_twap": (_TAPE + [_I32, _I32, _I32, _I32, _OUT], _I32),
+    "mxa_step": ([_P, _P, _P, _P], _I32),
+    "mxa_step_device": ([_P, _P, _P, _P], _I32),
+    "mxa_step_many": ([_P, _I32, _P, _P, _P], _I32),
+    "mxa_step_policy": ([_P, _I32, _I32, ctypes.POINTER(Policy), _P, _P, _P, _P, _P], _I32),
+    "mxa_set_parity_hash": ([_P, _I32], _I32),
+    "mxa_write_rl_state": ([_P, _P], _I32),
+    "mxa_build_id": ([], _S),
+    "mxa_set_book_log": ([_P, _I32], _I32),
+    "mxa_set_exchange_log": ([_P, _I32], _I32),
+    "mxa_read_book_log": ([_P, _I32, _P, _I64, _N64], _I32),
+    "mxa_rng_probe": ([_I32, _U32, _I32, _D, _D, _I32, _P], _I32),
+    "mxa_math_probe": ([_I32, _I32, _P, _P, _P, _I64], _I32),
+    "mxa_policy_probe": ([_P, _I32, _P, _P, _I32, _N32, _I32, _I32, _P, _P, _P, _P, _P], _I32),
+}
+EXPORTS = list(BINDINGS)
 COUNTER_WORDS = 34  # include/mxa.h MXA_COUNTER_WORDS
 INPLACE_WORDS = 4  # include/mxa.h MXA_INPLACE_WORDS
 RECORD_WORDS = 12  # include/mxa.h MXA_RECORD_WORDS
@@ -112,66 +169,10 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise MxaError("libmxa.so not built (%s); run __graft_entry__.build()" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    P, I32, I64, U32, D = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_double
-    L.mxa_create.argtypes = [I32, I32, P, I32, I32, ctypes.POINTER(P)]
-    L.mxa_reset.argtypes = [P, P]
-    L.mxa_launch.argtypes = [P, I64]
-    L.mxa_sync.argtypes = [P]
-    L.mxa_run.argtypes = [P, I64, I32, ctypes.POINTER(I32)]
-    L.mxa_read_summary.argtypes = [P, P]
-    L.mxa_read_agents.argtypes = [P, I32, P, I32]
-    L.mxa_read_book.argtypes = [P, I32, I32, P, I32]
-    L.mxa_read_trace.argtypes = [P, I32, P, I64, ctypes.POINTER(I64)]
-    L.mxa_n_agents.argtypes = [P]
-    L.mxa_n_envs.argtypes = [P]
-    L.mxa_env_bytes.argtypes = [P]
-    L.mxa_env_bytes.restype = I64
-    L.mxa_set_stream.argtypes = [P, P]
-    L.mxa_last_kernel_ms.argtypes = [P]
-    L.mxa_last_kernel_ms.restype = D
-    L.mxa_last_error.argtypes = [P]
-    L.mxa_last_error.restype = ctypes.c_char_p
-    L.mxa_destroy.argtypes = [P]
-    L.mxa_destroy.restype = None
-    L.mxa_set_seeds.argtypes = [P, P]
-    L.mxa_read_raw.argtypes = [P, I32, I64, I64, P]
-    L.mxa_layout.argtypes = [P, P]
-    L.mxa_write_results.argtypes = [P, P]
-    for name, args in (("mxa_write_records", [P, P]), ("mxa_set_id_persistence", [P, I32]),
-                       ("mxa_read_counters", [P, P]), ("mxa_read_inplace", [P, P]),
-                       ("mxa_create_hist", [I32, I32, P, I32, I32, P, P, I32, ctypes.POINTER(P)]),
-                       ("mxa_create_replay_runner", [P, P, P, P, P, I32, I32, I32, I32, ctypes.POINTER(P)]),
-                       ("mxa_set_stop_time", [P, I64]), ("mxa_run_until", [P, I64, P]),
-                       ("mxa_create_replay_twap", [P, P, P, P, P, I32, I32, I32, I32, I32, ctypes.POINTER(P)]),
-                       ("mxa_create_params", [I32, I32, P, P, I32, I32, ctypes.POINTER(P)]),
-                       ("mxa_set_mm_params", [P, P]), ("mxa_resident_envs", [P]),
-                       ("mxa_set_exchange_log", [P, I32]), ("mxa_set_launch_schedule", [P, I64]),
-                       ("mxa_config_defaults", [I32, P]), ("mxa_config_compile", [P, ctypes.c_char_p, P, I32]),
-                       ("mxa_config_key", [P, P]), ("mxa_config_info", [I32, P]),
-                       ("mxa_config_capacities", [P, P]),
-                       ("mxa_create_config", [P, I32, P, I32, I32, ctypes.c_char_p, ctypes.POINTER(P)])):
-        if hasattr(L, name):  # (older single-configuration A/B builds lack them; libmxa.so has all)
-            getattr(L, name).argtypes = args
-    L.mxa_write_rl_state.argtypes = [P, P]
-    L.mxa_set_parity_hash.argtypes = [P, I32]
-    L.mxa_rng_probe.argtypes = [I32, U32, I32, D, D, I32, P]
-    L.mxa_math_probe.argtypes = [I32, I32, P, P, P, I64]
-    L.mxa_create_replay.argtypes = [P, P, P, P, P, I32, I32, I32, I32, ctypes.POINTER(P)]
-    L.mxa_step.argtypes = [P, P, P, P]
-    L.mxa_step_device.argtypes = [P, P, P, P]
-    if hasattr(L, "mxa_step_many"):  # (A/B builds of earlier sources lack it; tests check the exports)
-        L.mxa_step_many.argtypes = [P, I32, P, P, P]
-    if hasattr(L, "mxa_step_policy"):  # (as mxa_step_many)
-        L.mxa_step_policy.argtypes = [P, I32, I32, ctypes.POINTER(Policy), P, P, P, P, P]
-        L.mxa_policy_probe.argtypes = [P, I32, P, P, I32, ctypes.POINTER(I32), I32, I32, P, P, P, P, P]
-    L.mxa_finalize.argtypes = [P]
-    L.mxa_read_final.argtypes = [P, I32, P, I32]
-    if hasattr(L, "mxa_set_book_log"):
-        L.mxa_set_book_log.argtypes = [P, I32]
-        L.mxa_read_book_log.argtypes = [P, I32, P, I64, ctypes.POINTER(I64)]
-    if hasattr(L, "mxa_build_id"):  # (absent from libraries built before it existed: A/B runs)
-        L.mxa_build_id.argtypes = []
-        L.mxa_build_id.restype = ctypes.c_char_p
+    for name, (argtypes, restype) in BINDINGS.items():
+        if hasattr(L, name):  # (MXA_LIB may name a variant build that lacks some)
+            f = getattr(L, name)
+            f.argtypes, f.restype = argtypes, restype
     _lib = L
     return L
 

@@ -25,10 +25,7 @@ BASES = {"rmsc03": _lib.MXA_RMSC03, "value_noise": _lib.MXA_VALUE_NOISE, "sparse
 BASE_NAMES = {v: k for k, v in BASES.items()}
 
 
-class MmParams(ctypes.Structure):  # include/mxa.h mxa_mm_params
-    _fields_ = [("mm_pov", ctypes.c_double), ("mm_min_order_size", ctypes.c_int32), ("mm_window_size", ctypes.c_int32),
-                ("mm_num_ticks", ctypes.c_int32), ("pad", ctypes.c_int32), ("mm_wake_up_freq_ns", ctypes.c_int64)]
-
+MmParams = _lib.MmParams  # include/mxa.h mxa_mm_params
 
 _I32, _I64, _D = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _G = ZI_GROUPS_MAX

@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .handle import Handle, seeds_u32
 from .tape import Tape, load_lobster
 
 OBS_SIZE = 9      # get_observation returns 9 values (the declared space says 10: dummy_rl:317-322)
@@ -22,16 +23,15 @@ ACTION_SIZE = 3   # order_level 2 -> [total volume, level-1 share, level-2 share
 RL_STATE_WORDS = 8  # mxa_write_rl_state row (include/mxa.h MXA_RL_STATE_WORDS)
 
 
-class VecABIDESEnv:
+class VecABIDESEnv(Handle):
     def __init__(self, tape=None, n_envs=None, device=0, trace_cap=0, seeds=None):
-        self.L = _lib.load()
+        Handle.__init__(self)
         self.tape = tape
         self.trace_cap = trace_cap
-        self._h = ctypes.c_void_p()
         if tape is None:  # rmsc03 + DummyRL, one env per seed
             if seeds is None:
                 raise TypeError("either a Tape or seeds (rmsc03 + DummyRL) is required")
-            sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+            sd = seeds_u32(seeds)
             if n_envs is not None and int(n_envs) != len(sd):
                 raise ValueError("n_envs must equal len(seeds)")
             self.n_envs = len(sd)
@@ -50,12 +50,6 @@ class VecABIDESEnv:
         self.obs = np.zeros((self.n_envs, OBS_SIZE), dtype=np.float64)
         self.flags = np.zeros(self.n_envs, dtype=np.int32)
 
-    def _check(self, rc, what):
-        if rc < 0:
-            msg = self.L.mxa_last_error(self._h).decode() if self._h else ""
-            raise _lib.MxaError("%s failed (%d): %s" % (what, rc, msg))
-        return rc
-
     def reset(self, seeds=None, mask=None):
         """ABIDESEnv.reset for every env (ABIDESEnv.py:51-57), or with `mask` ([n_envs], nonzero =
         reset) for the masked envs only: the others keep their episode, their seed and their
@@ -69,7 +63,7 @@ class VecABIDESEnv:
             if len(m) != self.n_envs:
                 raise ValueError("mask: one entry per env")
         if seeds is not None:  # rmsc03 + DummyRL: new per-env seeds (a full list; unmasked entries wait)
-            sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+            sd = seeds_u32(seeds)
             if len(sd) != self.n_envs:
                 raise ValueError("seeds: one per env")
             self._check(self.L.mxa_set_seeds(self._h, sd.ctypes.data), "mxa_set_seeds")
@@ -113,104 +107,13 @@ class VecABIDESEnv:
                                            ctypes.c_void_p(d_act), ctypes.c_void_p(d_state) if d_state else None),
                     "mxa_step_policy")
 
-    def set_parity_hash(self, on):
-        """Per-pop parity hash (summary()["hash"]) on or off; market results are identical
-        either way (include/mxa.h mxa_set_parity_hash)."""
-        self._check(self.L.mxa_set_parity_hash(self._h, 1 if on else 0), "mxa_set_parity_hash")
-
-    def set_stream(self, stream_ptr):
-        """Step on an external HIP stream (e.g. torch.cuda.current_stream().cuda_stream)."""
-        self._check(self.L.mxa_set_stream(self._h, ctypes.c_void_p(stream_ptr) if stream_ptr else None),
-                    "mxa_set_stream")
-
-    def write_results(self, device_ptr):
-        """Per-env (events, hash, status, current_time) int64 rows into device memory."""
-        self._check(self.L.mxa_write_results(self._h, ctypes.c_void_p(device_ptr)), "mxa_write_results")
-
-    def counters(self):
-        """[n_envs][COUNTER_WORDS] int64 event-class counters since the last reset (kept by
-        instrumented runs: parity hash on; include/mxa.h mxa_read_counters, mxabides.counters)"""
-        out = np.zeros((self.n_envs, _lib.COUNTER_WORDS), dtype=np.int64)
-        self._check(self.L.mxa_read_counters(self._h, out.ctypes.data), "mxa_read_counters")
-        return out
-
-    def inplace_groups(self):
-        """[market-maker query groups, value-agent wakes, cancel / ladder groups, 0] taken in place by
-        the instrumented runs (parity hash on) of this configuration's handles since the last call
-        (include/mxa.h mxa_read_inplace: read, then cleared).  The env blocks cannot tell: an in-place
-        group leaves every observable of the queued sequence"""
-        out = np.zeros(_lib.INPLACE_WORDS, dtype=np.uint64)
-        self._check(self.L.mxa_read_inplace(self._h, out.ctypes.data), "mxa_read_inplace")
-        return out
-
-    def write_records(self, device_ptr):
-        """Per-env episode records [n][RECORD_WORDS] int64 into device memory (include/mxa.h
-        mxa_write_records: events, hash, status, current_time, err, seed, last_trade, order_counter,
-        cash, holdings, gain, 0), the rows bench.py all-gathers across ranks."""
-        self._check(self.L.mxa_write_records(self._h, ctypes.c_void_p(device_ptr)), "mxa_write_records")
-
     def write_rl_state(self, device_ptr):
         """Per-env execution-agent state [n][RL_STATE_WORDS] float64 (CASH, holdings, executed,
         best bid, best ask, bid size, ask size, lob flags) into device memory, asynchronously."""
         self._check(self.L.mxa_write_rl_state(self._h, ctypes.c_void_p(device_ptr)), "mxa_write_rl_state")
 
-    def summary(self):
-        n = self.n_envs
-        buf = (_lib.EnvSummary * n)()
-        self._check(self.L.mxa_read_summary(self._h, buf), "mxa_read_summary")
-        return {"events": np.array([b.events for b in buf], dtype=np.int64),
-                "hash": np.array([b.hash for b in buf], dtype=np.uint64),
-                "status": np.array([b.status for b in buf], dtype=np.int32),
-                "err": np.array([b.err for b in buf], dtype=np.int32),
-                "current_time": np.array([b.current_time for b in buf], dtype=np.int64),
-                "order_counter": np.array([b.order_counter for b in buf], dtype=np.int64)}
-
     def agents(self, env):
-        n = self.n_agents
-        buf = (_lib.AgentState * n)()
-        self._check(self.L.mxa_read_agents(self._h, env, buf, n), "mxa_read_agents")
-        return [(b.cash, b.shares, b.n_open) for b in buf]
-
-    def book(self, env, side):
-        """levels best-first, FIFO within level: [[order_id, agent_id, qty, price], ...] per level"""
-        n = self._check(self.L.mxa_read_book(self._h, env, side, None, 0), "mxa_read_book")
-        buf = np.zeros((max(n, 1), 4), dtype=np.int64)
-        self._check(self.L.mxa_read_book(self._h, env, side, buf.ctypes.data, n), "mxa_read_book")
-        levels = []
-        for o in buf[:n].tolist():
-            if levels and levels[-1][0][3] == o[3]:
-                levels[-1].append(o)
-            else:
-                levels.append([o])
-        return levels
-
-    def trace(self, env):
-        out = np.zeros((self.trace_cap, 10), dtype=np.int64)
-        n = ctypes.c_int64()
-        self._check(self.L.mxa_read_trace(self._h, env, out.ctypes.data, self.trace_cap, ctypes.byref(n)),
-                    "mxa_read_trace")
-        return out[:n.value]
-
-    @property
-    def last_kernel_ms(self):
-        return self.L.mxa_last_kernel_ms(self._h)
-
-    @property
-    def resident_envs(self):
-        """envs resident on the device at once (step-kernel occupancy x CUs, at most n_envs;
-        include/mxa.h mxa_resident_envs)"""
-        return self._check(self.L.mxa_resident_envs(self._h), "mxa_resident_envs")
-
-    def close(self):
-        if self._h:
-            self.L.mxa_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return [(b.cash, b.shares, b.n_open) for b in self._agent_states(env)]
 
 
 class Box:

@@ -1,0 +1,124 @@
+"""Handle: what every libmxa handle (include/mxa.h mxa_handle) offers whichever constructor made
+it: the error check, the switches, the device-side writers and the readers.  VecMarket
+(mxabides.market, Kernel.runner handles) and VecABIDESEnv (mxabides.gym, GymKernel handles) derive
+from it; a subclass creates the handle into `self._h` and sets n_envs, n_agents and trace_cap."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+
+def seeds_u32(seeds):
+    """per-env seeds as the C-ABI takes them: the reference's -s values modulo 2^32"""
+    return np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+
+
+class Handle:
+    def __init__(self):
+        self.L = _lib.load()
+        self._h = ctypes.c_void_p()
+
+    def _check(self, rc, what):
+        if rc < 0:
+            msg = self.L.mxa_last_error(self._h).decode() if self._h else ""
+            raise _lib.MxaError("%s failed (%d): %s" % (what, rc, msg))
+        return rc
+
+    # ---- switches
+    def set_parity_hash(self, on):
+        """Per-pop parity hash (summary()["hash"]) on or off; market results are identical
+        either way (include/mxa.h mxa_set_parity_hash)."""
+        self._check(self.L.mxa_set_parity_hash(self._h, 1 if on else 0), "mxa_set_parity_hash")
+
+    def set_stream(self, stream_ptr):
+        """Run on an external HIP stream (e.g. torch.cuda.current_stream().cuda_stream)."""
+        self._check(self.L.mxa_set_stream(self._h, ctypes.c_void_p(stream_ptr) if stream_ptr else None),
+                    "mxa_set_stream")
+
+    # ---- device-side writers (asynchronous on the handle's stream)
+    def write_results(self, device_ptr):
+        """Per-env (events, hash, status, current_time) int64 rows into device memory."""
+        self._check(self.L.mxa_write_results(self._h, ctypes.c_void_p(device_ptr)), "mxa_write_results")
+
+    def write_records(self, device_ptr):
+        """Per-env episode records [n][RECORD_WORDS] int64 into device memory (include/mxa.h
+        mxa_write_records: events, hash, status, current_time, err, seed, last_trade, order_counter,
+        cash, holdings, gain, 0), the rows bench.py all-gathers across ranks."""
+        self._check(self.L.mxa_write_records(self._h, ctypes.c_void_p(device_ptr)), "mxa_write_records")
+
+    # ---- readers
+    def counters(self):
+        """[n_envs][COUNTER_WORDS] int64 event-class counters since the last reset (kept by
+        instrumented runs: parity hash on; include/mxa.h mxa_read_counters, mxabides.counters)"""
+        out = np.zeros((self.n_envs, _lib.COUNTER_WORDS), dtype=np.int64)
+        self._check(self.L.mxa_read_counters(self._h, out.ctypes.data), "mxa_read_counters")
+        return out
+
+    def inplace_groups(self):
+        """[market-maker query groups, value-agent wakes, cancel / ladder groups, 0] taken in place by
+        the instrumented runs (parity hash on) of this configuration's handles since the last call
+        (include/mxa.h mxa_read_inplace: read, then cleared).  The env blocks cannot tell: an in-place
+        group leaves every observable of the queued sequence"""
+        out = np.zeros(_lib.INPLACE_WORDS, dtype=np.uint64)
+        self._check(self.L.mxa_read_inplace(self._h, out.ctypes.data), "mxa_read_inplace")
+        return out
+
+    @property
+    def last_kernel_ms(self):
+        return self.L.mxa_last_kernel_ms(self._h)
+
+    @property
+    def resident_envs(self):
+        """envs resident on the device at once (run / step kernel occupancy x CUs, at most n_envs;
+        include/mxa.h mxa_resident_envs)"""
+        return self._check(self.L.mxa_resident_envs(self._h), "mxa_resident_envs")
+
+    def summary(self):
+        """every mxa_env_summary field as an [n_envs] array"""
+        arr = (_lib.EnvSummary * self.n_envs)()
+        self._check(self.L.mxa_read_summary(self._h, arr), "mxa_read_summary")
+        dt = {ctypes.c_int32: np.int32, ctypes.c_int64: np.int64, ctypes.c_uint64: np.uint64}
+        return {k: np.array([getattr(a, k) for a in arr], dtype=dt[t]) for k, t in _lib.EnvSummary._fields_}
+
+    def _agent_states(self, env):
+        arr = (_lib.AgentState * self.n_agents)()
+        self._check(self.L.mxa_read_agents(self._h, env, arr, self.n_agents), "mxa_read_agents")
+        return arr
+
+    def book(self, env, side):
+        """OrderBook.bids (side 0) / asks (side 1): list of levels best-first, each a FIFO list of
+        [order_id, agent_id, quantity, price]."""
+        cap = 4096
+        while True:  # mxa_read_book returns the side's order count; a replay book holds thousands
+            buf = np.zeros((cap, 4), dtype=np.int64)
+            n = self._check(self.L.mxa_read_book(self._h, env, side, buf.ctypes.data, cap), "mxa_read_book")
+            if n <= cap:
+                break
+            cap = n
+        levels = []
+        for o in buf[:n].tolist():
+            if levels and levels[-1][0][3] == o[3]:
+                levels[-1].append(o)
+            else:
+                levels.append([o])
+        return levels
+
+    def trace(self, env):
+        """env's trace ring rows [n][10] int64 (none without a trace ring)"""
+        buf = np.zeros((self.trace_cap, 10), dtype=np.int64)
+        n = ctypes.c_int64()
+        self._check(self.L.mxa_read_trace(self._h, env, buf.ctypes.data, self.trace_cap, ctypes.byref(n)),
+                    "mxa_read_trace")
+        return buf[:n.value]
+
+    def close(self):
+        if self._h:
+            self.L.mxa_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -10,13 +10,14 @@ import os
 import numpy as np
 
 from . import _lib
+from .handle import Handle, seeds_u32
 from .configs import (BOOK_FREQ, HIST_CONFIGS, MM_PARAMS_DTYPE, REPLAY_CONFIGS, agent_names, agent_type_names,
                       symbol_of)
 
 CHUNK_DEFAULT = 1 << 20
 
 
-class VecMarket:
+class VecMarket(Handle):
     def __init__(self, config, seeds, device=0, trace_cap=0, book_log=0, symbol=None, fundamental=None,
                  book_freq="config", tape=None, mm_params=None, exchange_log=False):
         """book_log: records per env of the book-update log (0 off), the input of the exchange's
@@ -40,18 +41,17 @@ class VecMarket:
         elif config not in _lib.CONFIG_IDS:
             raise ValueError("unknown config %r (supported: %s, or a composition.MarketConfig)" %
                              (config, sorted(_lib.CONFIG_IDS)))
-        self.L = _lib.load()
+        Handle.__init__(self)
         self.config = config
         if symbol is not None:
             symbol_of(config, symbol, tape)  # a fixed-symbol config refuses -t now, not at output time
         self._symbol = symbol
         self.tape = tape
         self.book_freq = BOOK_FREQ[config] if book_freq == "config" else book_freq
-        self.seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+        self.seeds = seeds_u32(seeds)
         self.n_envs = len(self.seeds)
         self.device = device
         self.trace_cap = trace_cap
-        self._h = ctypes.c_void_p()
         self.fundamental = fundamental
         if config in REPLAY_CONFIGS:
             if tape is None:
@@ -134,17 +134,6 @@ class VecMarket:
         self.mm_params = self._mm_array(mm_params)
         self._check(self.L.mxa_set_mm_params(self._h, self.mm_params.ctypes.data), "mxa_set_mm_params")
 
-    @property
-    def resident_envs(self):
-        """envs resident on the device at once (occupancy x CUs; include/mxa.h mxa_resident_envs)"""
-        return self._check(self.L.mxa_resident_envs(self._h), "mxa_resident_envs")
-
-    def _check(self, rc, what):
-        if rc < 0:
-            msg = self.L.mxa_last_error(self._h).decode() if self._h else ""
-            raise _lib.MxaError("%s failed (%d): %s" % (what, rc, msg))
-        return rc
-
     # ---- lifecycle
     def reset(self, mask=None):
         self._finalized = False
@@ -168,45 +157,9 @@ class VecMarket:
         self.exchange_log_on = bool(on)
 
     def set_seeds(self, seeds):
-        self.seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+        self.seeds = seeds_u32(seeds)
         assert len(self.seeds) == self.n_envs
         self._check(self.L.mxa_set_seeds(self._h, self.seeds.ctypes.data), "mxa_set_seeds")
-
-    def set_parity_hash(self, on):
-        """Per-pop parity hash (summary()["hash"]) on or off; market results are identical
-        either way (include/mxa.h mxa_set_parity_hash)."""
-        self._check(self.L.mxa_set_parity_hash(self._h, 1 if on else 0), "mxa_set_parity_hash")
-
-    def set_stream(self, stream_ptr):
-        """Run on an external HIP stream (e.g. torch.cuda.current_stream().cuda_stream)."""
-        self._check(self.L.mxa_set_stream(self._h, ctypes.c_void_p(stream_ptr) if stream_ptr else None),
-                    "mxa_set_stream")
-
-    def write_results(self, device_ptr):
-        """Per-env (events, hash, status, current_time) int64 rows into device memory."""
-        self._check(self.L.mxa_write_results(self._h, ctypes.c_void_p(device_ptr)), "mxa_write_results")
-
-    def counters(self):
-        """[n_envs][COUNTER_WORDS] int64 event-class counters since the last reset (kept by
-        instrumented runs: parity hash on; include/mxa.h mxa_read_counters, mxabides.counters)"""
-        out = np.zeros((self.n_envs, _lib.COUNTER_WORDS), dtype=np.int64)
-        self._check(self.L.mxa_read_counters(self._h, out.ctypes.data), "mxa_read_counters")
-        return out
-
-    def inplace_groups(self):
-        """[market-maker query groups, value-agent wakes, cancel / ladder groups, 0] taken in place by
-        the instrumented runs (parity hash on) of this configuration's handles since the last call
-        (include/mxa.h mxa_read_inplace: read, then cleared).  The env blocks cannot tell: an in-place
-        group leaves every observable of the queued sequence"""
-        out = np.zeros(_lib.INPLACE_WORDS, dtype=np.uint64)
-        self._check(self.L.mxa_read_inplace(self._h, out.ctypes.data), "mxa_read_inplace")
-        return out
-
-    def write_records(self, device_ptr):
-        """Per-env episode records [n][RECORD_WORDS] int64 into device memory (include/mxa.h
-        mxa_write_records: events, hash, status, current_time, err, seed, last_trade, order_counter,
-        cash, holdings, gain, 0), the rows bench.py all-gathers across ranks."""
-        self._check(self.L.mxa_write_records(self._h, ctypes.c_void_p(device_ptr)), "mxa_write_records")
 
     def launch(self, max_pops):
         self._check(self.L.mxa_launch(self._h, max_pops), "mxa_launch")
@@ -240,43 +193,13 @@ class VecMarket:
         return ev
 
     @property
-    def last_kernel_ms(self):
-        return self.L.mxa_last_kernel_ms(self._h)
-
-    @property
     def env_bytes(self):
         return self.L.mxa_env_bytes(self._h)
 
     # ---- inspection
-    def summary(self):
-        arr = (_lib.EnvSummary * self.n_envs)()
-        self._check(self.L.mxa_read_summary(self._h, arr), "mxa_read_summary")
-        dt = {ctypes.c_int32: np.int32, ctypes.c_int64: np.int64, ctypes.c_uint64: np.uint64}
-        return {k: np.array([getattr(a, k) for a in arr], dtype=dt[t]) for k, t in _lib.EnvSummary._fields_}
-
     def agents(self, env):
-        arr = (_lib.AgentState * self.n_agents)()
-        self._check(self.L.mxa_read_agents(self._h, env, arr, self.n_agents), "mxa_read_agents")
         return [dict(cash=a.cash, shares=a.shares, n_open=a.n_open, last_trade=a.last_trade, type=a.type,
-                     flags=a.flags, starting_cash=a.starting_cash) for a in arr]
-
-    def book(self, env, side):
-        """OrderBook.bids (side 0) / asks (side 1): list of levels, each a FIFO list of
-        [order_id, agent_id, quantity, price]."""
-        cap = 4096
-        while True:  # mxa_read_book returns the side's order count; a replay book holds thousands
-            buf = np.zeros((cap, 4), dtype=np.int64)
-            n = self._check(self.L.mxa_read_book(self._h, env, side, buf.ctypes.data, cap), "mxa_read_book")
-            if n <= cap:
-                break
-            cap = n
-        levels = []
-        for o in buf[:n].tolist():
-            if levels and levels[-1][0][3] == o[3]:
-                levels[-1].append(o)
-            else:
-                levels.append([o])
-        return levels
+                     flags=a.flags, starting_cash=a.starting_cash) for a in self._agent_states(env)]
 
     def layout(self):
         o = np.zeros(8, dtype=np.int64)
@@ -291,11 +214,7 @@ class VecMarket:
     def trace(self, env):
         if not self.trace_cap:
             raise ValueError("created with trace_cap=0")
-        buf = np.zeros((self.trace_cap, 10), dtype=np.int64)
-        n = ctypes.c_int64()
-        self._check(self.L.mxa_read_trace(self._h, env, buf.ctypes.data, self.trace_cap, ctypes.byref(n)),
-                    "mxa_read_trace")
-        return buf[:n.value]
+        return Handle.trace(self, env)
 
     def report(self, env):
         """The reference's end-of-run stdout: TradingAgent.kernelStopping "Final holdings"
@@ -475,14 +394,3 @@ class VecMarket:
         path = os.path.join(log_dir, "ORDERBOOK_%s_FULL.bz2" % self.symbol)
         self.orderbook_snapshots(env, wide_book).to_pickle(path, compression="bz2")
         return path
-
-    def close(self):
-        if self._h:
-            self.L.mxa_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
