@@ -279,11 +279,12 @@ int mxa_write_records(mxa_handle* h, void* device_out);
 int mxa_read_counters(mxa_handle* h, int64_t* out);
 /* In-place groups taken by the instrumented runs (parity hash on) of every handle of `h`'s
  * configuration in this process since the last call: [0] market-maker query groups (mm_cycle),
- * [1] value-agent wakes (value_cycle), [2] cancel / ladder groups (mm_ladder_cycle), [3] 0.  An
- * in-place group leaves every observable of the queued sequence in the env block, the counters
- * above included; this count is the one thing that tells the paths apart.  Reads, then clears.
- * Synchronous. */
-#define MXA_INPLACE_WORDS 4
+ * [1] value-agent wakes (value_cycle), [2] cancel / ladder groups (mm_ladder_cycle), [3] 0,
+ * [4] value agents' resting orders taken with their ORDER_ACCEPTED inside such a wake
+ * (value_order; at most [1]), [5] 0.  An in-place group leaves every observable of the queued
+ * sequence in the env block, the counters above included; this count is the one thing that tells
+ * the paths apart.  Reads, then clears.  Synchronous. */
+#define MXA_INPLACE_WORDS 6
 int mxa_read_inplace(mxa_handle* h, uint64_t* out);
 /* diagnostics: copy `bytes` raw bytes of env `env`'s HBM block starting at `offset`; and
  * the block's section offsets (Layout: ag, open, rng, lat, q, book, tx, trace) */

@@ -112,6 +112,16 @@ constexpr Shape shape(int cfg);
 #ifndef MXA_SYNC_VALUE_MASK
 #define MXA_SYNC_VALUE_MASK MXA_SYNC_QUERY_MASK
 #endif
+// ... and whose value agents' resting LIMIT_ORDER and its ORDER_ACCEPTED ride in that pop as well
+// (Eng::value_order; needs the value bit too)
+#ifndef MXA_SYNC_ORDER_MASK
+#define MXA_SYNC_ORDER_MASK MXA_SYNC_QUERY_MASK
+#endif
+// 1: the order enters the book in place but its ORDER_ACCEPTED is still pushed and popped (the A/B
+// variant of Appendix R.11)
+#ifndef MXA_ORDER_ACK_QUEUED
+#define MXA_ORDER_ACK_QUEUED 0
+#endif
 // ... and whose market maker's cancel and ladder runs, with the exchange's replies to them, ride in
 // the same pop when the volume reply re-quotes (Eng::mm_ladder_cycle; needs the query bit too)
 #ifndef MXA_SYNC_LADDER_MASK

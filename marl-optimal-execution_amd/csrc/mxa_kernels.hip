@@ -2936,7 +2936,11 @@ struct Eng {
     }
     return true;
   }
-  DEV void value_place() {
+  // INPL (Eng::value_cycle only): an order that rests on the book the reply was just read from may be
+  // taken in place with its ORDER_ACCEPTED (value_order; room: the pops this launch may still make
+  // after the group's own); returns the pops taken beyond the reply's
+  template <bool INPL = false>
+  DEV int value_place(i64 room = 0) {
     i64 obs = o_observe(cur, v_sigma_n());
     i64 r_T = bayes_r_T(obs, PC.v_kappa, v_rbar(), v_sigma_n(), PC.v_sigma_s);
     i32 bid, ask;
@@ -2963,15 +2967,28 @@ struct Eng {
       p = r_T;
     }
     grs_put(0, G);
+    if constexpr (INPL) {
+      // both insides known: bid / ask are the best prices of the book as it stands (the reply was
+      // built from it in this pop), so the exchange's match test is a compare.  A one-sided book
+      // takes the queued path
+      if (hb && ha) {
+        const i32 pi = (i32)p;
+        return value_order(rgi(AF_SIZE), buy, pi, buy ? pi < ask : pi > bid, room);
+      }
+    }
     place_limit(rgi(AF_SIZE), buy, p);
+    return 0;
   }
-  DEV void value_receive(const Msg& m) {
+  template <bool INPL = false>
+  DEV int value_receive(const Msg& m, i64 room = 0) {
     ta_receive(m, AG_VALUE);
+    int n = 0;
     if (rgi(AF_STATE) == AS_AWAITING_SPREAD && m_kind(m) == MK_SPREAD) {
-      if (fl(FL_MKT_CLOSED)) return;
-      value_place();
+      if (fl(FL_MKT_CLOSED)) return 0;
+      n = value_place<INPL>(room);
       rs(AF_STATE, AS_AWAITING_WAKEUP);
     }
+    return n;
   }
 
   // ---------------- NoiseAgent (NoiseAgent.py:82-154)
@@ -4617,7 +4634,7 @@ struct Eng {
       if constexpr (PC.n_noise > 0)
         if (type == AG_NOISE) return noise_receive(m);
       if constexpr (PC.n_value > 0)
-        if (type == AG_VALUE) return value_receive(m);
+        if (type == AG_VALUE) return (void)value_receive(m);
       if constexpr (PC.n_mm > 0)
         if (type == AG_POVMM) return mm_receive(m);
       if constexpr (PC.n_mom > 0)
@@ -5420,7 +5437,8 @@ struct Eng {
   // (t, agent + 1) (the agent's own next wakeup, just set, included) the forced pops are: the CANCEL_ORDER and the
   // QUERY_SPREAD at the exchange, then ORDER_CANCELLED (if the order still rested: del orders[id],
   // the fast path of the event loop) and the spread reply at the agent, whose handler places the
-  // new order.  That LIMIT_ORDER is sent as an event: it can cross and fan out executions.
+  // new order.  A LIMIT_ORDER that can cross is sent as an event (it fans out executions); one that
+  // rests is taken here with its ORDER_ACCEPTED (value_order below, MXA_SYNC_ORDER_MASK).
   // More than one open order, or a list longer than one 64-entry chunk, takes the queued path.
   static constexpr bool SYNCV = SYNCQ_BASE && ((((MXA_SYNC_VALUE_MASK)) >> CFG) & 1) && PC.n_value > 0;
   DEV int value_cycle(i64 t, i64 budget) {
@@ -5484,8 +5502,69 @@ struct Eng {
     if (instr && lane == 0) h.kc[MXA_KC_REC] += found ? 2 : 1;  // the replies' record round trips
     rs(AF_STATE, AS_AWAITING_SPREAD);
     if (MXA_RARE(dirty)) rng_maint();  // the wakeup's own event boundary, before the reply's draws
+    if constexpr (SYNCO) return np + value_receive<true>(r, budget - 1 - np);
     value_receive(r);
     return np;
+  }
+  // ---------------- the value agent's resting order and its acknowledgement in place
+  // The reply's handler ends value_cycle's group by placing the agent's one order: a LIMIT_ORDER at
+  // (t, 0, MESSAGE), the smallest key there is, so it is the forced next pop (nothing was pending
+  // before (t, agent + 1) and the group pushed nothing).  If it rests, the exchange enters it and
+  // pushes only ORDER_ACCEPTED at (t, agent, MESSAGE), again the only event before the bound, whose
+  // whole effect is agentCurrentTimes[agent] = t (ACK_FAST).  Both ride in the wakeup's pop when,
+  // decided before the first effect: the order rests (`rests`: the caller's compare against the
+  // inside of the book as the wake's own cancel left it; crossing orders fan out executions to
+  // third agents and stay queued), qty > 0, the book has a free slot (an overflow fails in the
+  // queued pop, where the reference's does), the open-order list takes the entry without
+  // compaction, and the launch budget covers the two pops (room).  value_cycle's own conditions
+  // (t <= close, t <= stopTime, agent < ACK_LIMIT, the bound, a running env) held at its head and
+  // nothing since has pushed or failed.  Anything else is place_limit_oid as it is.
+  // The agent's side is place_limit_oid's; the exchange's is a resting handle_limit through the
+  // ladder group's book entry (ex_limit_book: free slot, arrival stamp, history epoch, per-epoch
+  // entry count and order-history record of one-by-one entry).  The two pops are accounted in
+  // pop order with the messages send_ex and ex_notify would have queued, seq moves by their two
+  // pushes, and no record round trip is counted (neither queued pop loads a record).  The
+  // exchange's agentCurrentTimes is t already (value_cycle stored it for this group) and the
+  // agent's becomes t + 0 when the wakeup's pop ends, which is what the ORDER_ACCEPTED leaves.
+  // The queue's high-water mark needs no update: when the queued sequence pushes the order, the
+  // group's k + 1 earlier messages have all been popped, so it holds qcount + 1 events, and
+  // again qcount + 1 with the ORDER_ACCEPTED; value_cycle took the peak qcount + k + 1 at its head.
+  // MXA_ORDER_ACK_QUEUED: the measured variant whose ORDER_ACCEPTED is still pushed and popped.
+  static constexpr bool SYNCO = SYNCV && ((((MXA_SYNC_ORDER_MASK)) >> CFG) & 1);
+  static constexpr bool ORDER_AQ = MXA_ORDER_ACK_QUEUED != 0;
+  DEV int value_order(i64 qty, int is_buy, i32 price, bool rests, i64 room) {
+    const i64 oid = next_order_id();
+    const i32 n = rgi(AF_NORD), u = rgi(AF_NUSED);
+    const bool ok = rests && qty > 0 && room >= 2 && h.b_count < SO * 64 && n < PC.L.open_cap && u < PC.L.open_cap &&
+                    status == ST_RUNNING;
+    if (!ok) {
+      place_limit_oid(qty, is_buy, price, oid);
+      return 0;
+    }
+    PROF_CNT(116);  // value orders taken in place (of the in-place value-agent wakes)
+    note_inplace(4);
+    if (lane == 0) {
+      OpenOrder o;
+      o.oid = (i32)oid;
+      o.is_buy = is_buy;
+      o.qty = (i32)qty;
+      o.price = price;
+      open_ptr(cur_agent)[u] = o;
+    }
+    rs(AF_NUSED, (u32)(u + 1));
+    rs(AF_NORD, (u32)(n + 1));
+    const u64 kag = ((u64)cur << KSH) | ((u64)cur_agent << 2) | MT_MESSAGE;
+    const Msg am = msg_order(MK_ACCEPTED, (i32)oid, cur_agent, is_buy, (i32)qty, price, 0);
+    if (INSTR && (hash_on || trace)) {
+      account_pop(cur, ((u64)cur << KSH) | MT_MESSAGE, msg_order(MK_LIMIT, (i32)oid, cur_agent, is_buy, (i32)qty, price, 0));
+      if constexpr (!ORDER_AQ) account_pop(cur, kag, am);
+    } else {
+      pops += ORDER_AQ ? 1 : 2;
+    }
+    if constexpr (ORDER_AQ) q_push(kag, seq + 1, am);
+    seq += 2;
+    ex_limit_book(lane == 0, is_buy, price, (i32)oid, cur_agent, (i32)qty);
+    return ORDER_AQ ? 1 : 2;
   }
 
   DEV void run(i64 max_pops) {

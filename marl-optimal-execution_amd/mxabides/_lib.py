@@ -152,7 +152,7 @@ BINDINGS = {
 }
 EXPORTS = list(BINDINGS)
 COUNTER_WORDS = 34  # include/mxa.h MXA_COUNTER_WORDS
-INPLACE_WORDS = 4  # include/mxa.h MXA_INPLACE_WORDS
+INPLACE_WORDS = 6  # include/mxa.h MXA_INPLACE_WORDS
 RECORD_WORDS = 12  # include/mxa.h MXA_RECORD_WORDS
 
 _lib = None

@@ -56,7 +56,8 @@ class Handle:
         return out
 
     def inplace_groups(self):
-        """[market-maker query groups, value-agent wakes, cancel / ladder groups, 0] taken in place by
+        """[market-maker query groups, value-agent wakes, cancel / ladder groups, 0, value agents'
+        resting orders with their acknowledgement (inside such a wake), 0] taken in place by
         the instrumented runs (parity hash on) of this configuration's handles since the last call
         (include/mxa.h mxa_read_inplace: read, then cleared).  The env blocks cannot tell: an in-place
         group leaves every observable of the queued sequence"""

@@ -53,6 +53,8 @@ print("in-place groups      MM %d of %d wakes (%.1f%%), VALUE %d of %d wakes (%.
       % (v[76], v[25], 100.0 * v[76] / max(v[25], 1), v[108], v[23], 100.0 * v[108] / max(v[23], 1)))
 # ... and the market maker's cancel / ladder group with it (Eng::mm_ladder_cycle, count 111)
 print("in-place ladder      MM %d of %d wakes (%.1f%%)" % (v[111], v[25], 100.0 * v[111] / max(v[25], 1)))
+# ... and the value agents' resting order with its ORDER_ACCEPTED (Eng::value_order, count 116)
+print("in-place value order VALUE %d of %d in-place wakes (%.1f%%)" % (v[116], v[108], 100.0 * v[116] / max(v[108], 1)))
 print("inclusive function timers (nested inside the phases above; cycles per call)")
 for slot, nm in [(64, "send"), (65, "q_push"), (66, "handle_limit"), (67, "cancel_order"), (68, "b_best"),
                  (69, "o_observe"), (70, "bayes_r_T"), (71, "cancel_all"), (72, "place_limit"), (73, "ex_receive"),
