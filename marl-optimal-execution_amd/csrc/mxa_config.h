@@ -229,6 +229,26 @@ constexpr int book_lds(int cfg) {
          : (cfg >= MXA_CFG_RANDOM_FUND_VALUE && cfg <= MXA_CFG_HIST_FUND_DIVERSE) ? MXA_BOOK_LDS_RFV
                                                                                  : 0;
 }
+// The RNG stream windows (DESIGN.md §3 "RNG stream windows", Appendix R.12; bit = config id).  A unit
+// outside the first mask compiles to the code it had before it.
+// ... whose windows hold tempered outputs, so a draw is the LDS read alone (MXA_TEMPER_AT_FILL 0:
+// nowhere).  A bit is set where the configuration was measured with it and passed: rmsc03 x4096
+// 20.81 -> 20.34 ms; with the next mask's bit sparse_zi_100 104.2 -> 101.0, value_noise 17.1 -> 16.0.
+// rmsc01 neutral, off; rmsc03_rl loses with it (21.76 -> 22.31), off
+#ifndef MXA_TEMPER_FILL_MASK
+#define MXA_TEMPER_FILL_MASK ((1 << MXA_CFG_RMSC03) | (1 << MXA_CFG_SPARSE_ZI_100) | (1 << MXA_CFG_VALUE_NOISE))
+#endif
+// ... whose o_observe calls o_advance once (MXA_ONE_ADVANCE 0: nowhere).  This part did NOT pass the
+// A/B rule on its own (rmsc03: every run below every run of the parent, but 0.12 ms under its fastest
+// against a spread of 0.19) and is neutral in time on top of the tempered fill.  It is on wherever
+// the fill is, against "a part that does not pass stays off", for what it does to the code: the fill
+// alone grows the rmsc03 run kernel's VGPR spills 226 -> 248, with this they are 219, SGPR spills
+// 56 -> 42, 31.6 k -> 27.2 k static instructions, 166 -> 142 kB
+#ifndef MXA_ONE_ADVANCE_MASK
+#define MXA_ONE_ADVANCE_MASK MXA_TEMPER_FILL_MASK
+#endif
+constexpr bool temper_fill(int cfg) { return (((MXA_TEMPER_FILL_MASK) >> cfg) & 1) != 0; }
+constexpr bool one_advance(int cfg) { return (((MXA_ONE_ADVANCE_MASK) >> cfg) & 1) != 0; }
 constexpr size_t lds_bytes(int cfg) {
   return (size_t)sq_lds(cfg) * 64 * (12 + (shape(cfg).pl ? 4 * shape(cfg).pw : 0)) + 512  // queue + EnvHdr
          + (size_t)shape(cfg).hot * 512                                                       // hot agent records

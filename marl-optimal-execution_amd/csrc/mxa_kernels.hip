@@ -214,16 +214,22 @@ DEV u64 as_u(double x) { return __builtin_bit_cast(u64, x); }
 // (BUILD = true) materializes blocks on demand instead.
 #define LDSP __attribute__((address_space(3)))
 #define GLBP __attribute__((address_space(1)))
-template <bool BUILD>
+// How a stream's draws read its words.  RS_WIN: a 64-word window of its outputs in LDS (lw);
+// RS_HBM: the MT block in HBM, one dependent load per word; RS_PTR: decided per draw by lw != nullptr,
+// both paths compiled at every site (the units outside MXA_TEMPER_FILL_MASK, whose code is left as
+// it was measured, and the RNG probe kernel).
+// TF: the window holds tempered outputs (MXA_TEMPER_FILL_MASK)
+enum { RS_PTR = 0, RS_WIN = 1, RS_HBM = 2 };
+template <bool BUILD, int W = RS_PTR, bool TF = false>
 struct RSt {
   u32* key;
   i32 p;      // absolute output index since seeding (first output: p = 624)
   i32 m;      // highest materialized block
   i32 hasg;   // bit0: cached second gauss (legacy_gauss); bit1: look-ahead overrun
   double gauss;
-  // run kernel, global streams G/O/K/L: a 64-word window of the stream's outputs in LDS (words
-  // lw0 .. lw0 + lwn - 1, untempered), so a draw is an LDS read instead of an HBM round trip;
-  // lw == nullptr: draws read the MT block in HBM (agent streams, the build kernel)
+  // the window holds the stream's outputs lw0 .. lw0 + lwn - 1 (tempered with TF, the state words
+  // otherwise), so a draw is an LDS read instead of an HBM round trip.  The run kernel's global
+  // streams G/O/K/L keep theirs for a launch; the build kernel fills on demand
   LDSP u32* lw;
   i32 lw0, lwn;
 };
@@ -335,16 +341,37 @@ DEV void mt_seed(u32* key, u32 s) {
 #ifndef MXA_BUILD_WINDOWS
 #define MXA_BUILD_WINDOWS 1
 #endif
+// 1: the configurations of MXA_TEMPER_FILL_MASK keep tempered outputs in their windows (the four
+// xor-shift steps run once per fill, 64 lanes wide on the VALU) and a draw is the LDS read alone;
+// elsewhere, and with 0 everywhere, a window holds the state words and every draw tempers its
+// word on the scalar unit
+#ifndef MXA_TEMPER_AT_FILL
+#define MXA_TEMPER_AT_FILL 1
+#endif
+// 1: in the configurations of MXA_ONE_ADVANCE_MASK o_observe clamps the time and calls o_advance
+// once; elsewhere, and with 0 everywhere, one call per side of the clamp, which inlines the
+// oracle's advance twice into every value_place (Appendix R.12)
+#ifndef MXA_ONE_ADVANCE
+#define MXA_ONE_ADVANCE 1
+#endif
+DEV u32 mt_temper(u32 y) {
+  y ^= (y >> 11);
+  y ^= (y << 7) & 0x9d2c5680u;
+  y ^= (y << 15) & 0xefc60000u;
+  y ^= (y >> 18);
+  return y;
+}
 // refill a stream window from position p: lane i loads output word p + i if its block is in
 // the double buffer (materialized and not yet overwritten); the window ends at the first word
 // that is not, and an empty window is the look-ahead overrun
-template <bool B>
-DEV void rs_fill(RSt<B>& r) {
+template <bool B, int W, bool TF>
+DEV void rs_fill(RSt<B, W, TF>& r) {
   const int lane = laneid();
   const int q = r.p + lane, b = q / MXA_MT_N;
   const bool ok = b <= r.m && b >= r.m - 1;
   u32 v = 0;
   if (ok) v = r.key[(b & 1) * MXA_MT_N + (q - b * MXA_MT_N)];
+  if constexpr (TF) v = mt_temper(v);
   r.lw[lane] = v;
   const u64 okb = __ballot(ok);
   r.lwn = ~okb == 0 ? 64 : __ffsll((unsigned long long)~okb) - 1;
@@ -352,10 +379,10 @@ DEV void rs_fill(RSt<B>& r) {
   if (r.lwn == 0) r.hasg |= 2;
   __threadfence_block();
 }
-template <bool B>
-DEV u32 rs_u32(RSt<B>& r) {
-  if constexpr (!B || MXA_BUILD_WINDOWS) {
-    if (r.lw) {
+template <bool B, int W, bool TF>
+DEV u32 rs_u32(RSt<B, W, TF>& r) {
+  if constexpr (W == RS_WIN || (W == RS_PTR && (!B || MXA_BUILD_WINDOWS))) {
+    if (W == RS_WIN || r.lw) {
       u32 off = (u32)(r.p - r.lw0);
       if (MXA_RARE(off >= (u32)r.lwn)) {  // the window refill: one word in 64
         if constexpr (B) {  // the build materializes blocks as it draws
@@ -370,13 +397,11 @@ DEV u32 rs_u32(RSt<B>& r) {
       }
       u32 y = r.lw[off];
       r.p++;
-      y ^= (y >> 11);
-      y ^= (y << 7) & 0x9d2c5680u;
-      y ^= (y << 15) & 0xefc60000u;
-      y ^= (y >> 18);
+      if constexpr (!TF) y = mt_temper(y);
       return y;
     }
   }
+  if constexpr (W == RS_WIN) __builtin_unreachable();
   int blk = r.p / MXA_MT_N;
   if (B) {
     while (r.m < blk) {
@@ -388,20 +413,16 @@ DEV u32 rs_u32(RSt<B>& r) {
   }
   u32 y = r.key[(blk & 1) * MXA_MT_N + (r.p - blk * MXA_MT_N)];
   r.p++;
-  y ^= (y >> 11);
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= (y >> 18);
-  return y;
+  return mt_temper(y);
 }
-template <bool B>
-DEV double rs_double(RSt<B>& r) {
+template <bool B, int W, bool TF>
+DEV double rs_double(RSt<B, W, TF>& r) {
   i32 a = (i32)(rs_u32(r) >> 5);
   i32 b = (i32)(rs_u32(r) >> 6);
   return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
 }
-template <bool B>
-DEV i64 rs_randint(RSt<B>& r, i64 lo, i64 hi) {
+template <bool B, int W, bool TF>
+DEV i64 rs_randint(RSt<B, W, TF>& r, i64 lo, i64 hi) {
   u64 rng = (u64)(hi - lo - 1);
   if (rng == 0) return lo;
   if (rng == 0xFFFFFFFFull) return lo + (i64)rs_u32(r);
@@ -417,12 +438,12 @@ DEV i64 rs_randint(RSt<B>& r, i64 lo, i64 hi) {
 // candidates across the wave in one load round trip) was built, checked bit-exact and measured in
 // round 4: neutral on sparse_zi_1000 (721.9 vs 722 ms) and rmsc02's run kernel grew (62.1 k vs
 // 54.4 k instructions); removed in round 5
-template <bool B>
-DEV double rs_gauss(RSt<B>& r) {
+template <bool B, int W, bool TF>
+DEV double rs_gauss(RSt<B, W, TF>& r) {
   return rs_gauss_serial(r);
 }
-template <bool B>
-DEV double rs_gauss_serial(RSt<B>& r) {
+template <bool B, int W, bool TF>
+DEV double rs_gauss_serial(RSt<B, W, TF>& r) {
   if (r.hasg & 1) {
     double t = r.gauss;
     r.hasg &= ~1;
@@ -440,14 +461,15 @@ DEV double rs_gauss_serial(RSt<B>& r) {
   r.hasg |= 1;
   return f * x2;
 }
-template <bool B>
-DEV double rs_normal(RSt<B>& r, double loc, double scale) { return loc + scale * rs_gauss(r); }
-template <bool B>
-DEV double rs_exponential(RSt<B>& r, double scale) { return scale * -gm_log(1.0 - rs_double(r)); }
-template <bool B>
-DEV double rs_uniform(RSt<B>& r, double lo, double hi) { return lo + (hi - lo) * rs_double(r); }
+template <bool B, int W, bool TF>
+DEV double rs_normal(RSt<B, W, TF>& r, double loc, double scale) { return loc + scale * rs_gauss(r); }
+template <bool B, int W, bool TF>
+DEV double rs_exponential(RSt<B, W, TF>& r, double scale) { return scale * -gm_log(1.0 - rs_double(r)); }
+template <bool B, int W, bool TF>
+DEV double rs_uniform(RSt<B, W, TF>& r, double lo, double hi) { return lo + (hi - lo) * rs_double(r); }
 // advance by k outputs without tempering them (build kernel only)
-DEV void rs_skip_words(RSt<true>& r, i64 k) {
+template <int W, bool TF>
+DEV void rs_skip_words(RSt<true, W, TF>& r, i64 k) {
   i64 target = (i64)r.p + k;
   while ((i64)r.m < target / MXA_MT_N) {
     mt_gen_build(r.key, r.m + 1);
@@ -475,8 +497,8 @@ DEV void rs_skip_words(RSt<true>& r, i64 k) {
 #ifndef MXA_AGENT_LA
 #define MXA_AGENT_LA 256
 #endif
-template <bool B>
-DEV void rs_maint(RSt<B>& r, int la = MXA_MT_N) {
+template <bool B, int W, bool TF>
+DEV void rs_maint(RSt<B, W, TF>& r, int la = MXA_MT_N) {
   while (r.m < (r.p + la) / MXA_MT_N) {
     if constexpr (B) mt_gen_build(r.key, r.m + 1);
     else mt_gen_block(r.key, r.m + 1);
@@ -773,7 +795,16 @@ struct Eng {
   // the CANCELLED shortcut (open-order list) stays off
   static constexpr bool RP_FAST = !BUILD && RP && PC.default_comp_delay == 0 && PC.ex_comp == 0;
   static constexpr int ACK_LIMIT = GYM ? PC.first_rl : PC.n_agents;  // background agents 1..ACK_LIMIT-1
-  typedef RSt<BUILD> RS;
+  // RNG stream handles.  A unit with the tempered fill knows at compile time how each stream
+  // reads: G/O/K/L (RS) through their windows (the build kernel's follow MXA_BUILD_WINDOWS), an
+  // agent's own stream (ARS, Agent.random_state) from HBM; the build kernel's agent draws go
+  // through the L window.  Every other unit keeps the one handle type whose draws test the window
+  // pointer (RS_PTR): its code is the code it was measured with
+  static constexpr bool TFILL = MXA_TEMPER_AT_FILL != 0 && mxa_cfg::temper_fill(CFG);
+  static constexpr bool ONE_ADV = MXA_ONE_ADVANCE != 0 && mxa_cfg::one_advance(CFG);
+  typedef typename std::conditional<TFILL, RSt<BUILD, (!BUILD || MXA_BUILD_WINDOWS != 0) ? RS_WIN : RS_HBM, true>,
+                                    RSt<BUILD>>::type RS;
+  typedef typename std::conditional<BUILD || !TFILL, RS, RSt<false, RS_HBM, true>>::type ARS;
   typedef typename std::conditional<PL_LDS, LDSP u32*, u32*>::type PlPtr;
   static constexpr int QCAP = SQ * 64;
   // event key t << KSH | recipient << 2 | type (13 recipient bits: random_fund_value's 5,101 agents)
@@ -1106,8 +1137,8 @@ struct Eng {
   }
 
   // agent RNG stream (Agent.random_state): key words in HBM, pos/gauss cache in the record
-  DEV RS agent_rs() {
-    RS r;
+  DEV ARS agent_rs() {
+    ARS r;
     r.lw = BUILD && MXA_BUILD_WINDOWS ? rwin + 3 * 64 : nullptr;
     r.lw0 = r.lwn = 0;
     r.key = rng_key(4 + cur_agent);
@@ -1117,7 +1148,7 @@ struct Eng {
     r.gauss = rgd(AF_RS_GAUSS);
     return r;
   }
-  DEV void agent_rs_put(const RS& r) {
+  DEV void agent_rs_put(const ARS& r) {
     rs(AF_RS_POS, (u32)r.p);
     rs(AF_RS_M, (u32)r.m);
     rs(AF_RS_HASG, (u32)r.hasg);
@@ -1127,7 +1158,8 @@ struct Eng {
   // whether rng_maint has work for a stream in this state: a look-ahead overrun to report, or
   // no materialized block after the one holding position p.  Decided where the state is put
   // (registers) instead of re-read from the header and the record at the event's end
-  DEV bool rs_needs_maint(const RS& r, int la = MXA_MT_N) {
+  template <int W, bool TF>
+  DEV bool rs_needs_maint(const RSt<BUILD, W, TF>& r, int la = MXA_MT_N) {
     if constexpr (BUILD) return true;
     return (r.hasg & 2) || r.m < (r.p + la) / MXA_MT_N;
   }
@@ -1205,13 +1237,26 @@ struct Eng {
       if (MXA_UNLIKELY(hg & 2)) fail(ERR_RNG_OVERRUN);
       const int la = k < 4 ? MXA_MT_N : MXA_AGENT_LA;
       if (!MXA_RARE(m < (p + la) / MXA_MT_N)) continue;  // the look-ahead is there (almost always)
-      RS r = kr ? grs_k() : k < 4 ? grs(k) : agent_rs();
-      rs_maint(r, la);
-      if (kr) {
-        km = r.m;
+      // (two forms of one body: a unit with one handle type keeps the statement its code was measured
+      // with; a single form for both moved the rmsc03 run kernel's register allocation, unmeasured)
+      if constexpr (std::is_same<RS, ARS>::value) {
+        RS r = kr ? grs_k() : k < 4 ? grs(k) : agent_rs();
+        rs_maint(r, la);
+        if (kr) {
+          km = r.m;
+        } else if (k < 4) {
+          h.rs_m[k] = r.m;
+        } else {
+          rs(AF_RS_M, (u32)r.m);
+        }
       } else if (k < 4) {
-        h.rs_m[k] = r.m;
+        RS r = kr ? grs_k() : grs(k);
+        rs_maint(r, la);
+        if (kr) km = r.m;
+        else h.rs_m[k] = r.m;
       } else {
+        ARS r = agent_rs();
+        rs_maint(r, la);
         rs(AF_RS_M, (u32)r.m);
       }
     }
@@ -1835,14 +1880,16 @@ struct Eng {
     if constexpr (EXT) {  // ExternalFileOracle.observePrice (ExternalFileOracle.py:110-129): no clamp, no draws
       const double tp = efo_price(t);
       if (sigma_n == 0) return py_round(tp);
-      RS A = agent_rs();
+      ARS A = agent_rs();
       const i64 obs = py_round(rs_normal(A, tp, __builtin_sqrt(sigma_n)));
       agent_rs_put(A);
       return obs;
     }
-    double r_t = t >= PC.mkt_close ? o_advance(PC.mkt_close - 1) : o_advance(t);
+    double r_t;
+    if constexpr (ONE_ADV) r_t = o_advance(t >= PC.mkt_close ? PC.mkt_close - 1 : t);  // one inlined copy
+    else r_t = t >= PC.mkt_close ? o_advance(PC.mkt_close - 1) : o_advance(t);
     if (sigma_n == 0) return (i64)r_t;
-    RS A = agent_rs();
+    ARS A = agent_rs();
     i64 obs = py_round(rs_normal(A, r_t, __builtin_sqrt(sigma_n)));
     agent_rs_put(A);
     return obs;
@@ -2672,7 +2719,7 @@ struct Eng {
     if constexpr (GYM) {
       if (type == AG_DUMMYRL) return PC.rl_h0 - PC.mkt_open;     // execution_agent.py:129-130
     }
-    RS A = agent_rs();
+    ARS A = agent_rs();
     i64 v = rs_randint(A, 0, 100);
     agent_rs_put(A);
     return v;
@@ -2839,7 +2886,7 @@ struct Eng {
     if (!fl(FL_HAS_OPEN) || !fl(FL_HAS_CLOSE)) return;
     fl_set(FL_TRADING, true);
     if (fl(FL_MKT_CLOSED) && fl(FL_DAILY_CLOSE)) return;
-    RS A = agent_rs();
+    ARS A = agent_rs();
     double dt = rs_exponential(A, 1.0 / PC.zi_lambda);
     agent_rs_put(A);
     wakeup_at(cur_agent, cur + py_round(dt));
@@ -2865,7 +2912,7 @@ struct Eng {
     if (q >= PC.zi_qmax) buy = 0;
     else if (q <= -PC.zi_qmax) buy = 1;
     else {
-      RS A = agent_rs();
+      ARS A = agent_rs();
       buy = (int)rs_randint(A, 0, 2);
       agent_rs_put(A);
     }
@@ -2885,7 +2932,7 @@ struct Eng {
     int buy;
     if (!zi_update_estimates(v, buy)) return;
     int g = rgi(AF_GROUP);
-    RS A = agent_rs();
+    ARS A = agent_rs();
     i64 R = rs_randint(A, PC.zi_rmin[g], (i64)PC.zi_rmax[g] + 1);
     agent_rs_put(A);
     i64 p = buy ? v - R : v + R;
@@ -2925,7 +2972,7 @@ struct Eng {
     if (!fl(FL_HAS_OPEN) || !fl(FL_HAS_CLOSE)) return false;
     fl_set(FL_TRADING, true);
     if (fl(FL_MKT_CLOSED) && fl(FL_DAILY_CLOSE)) return false;
-    RS A = agent_rs();
+    ARS A = agent_rs();
     double dt = rs_exponential(A, 1.0 / PC.v_lambda);
     agent_rs_put(A);
     wakeup_at(cur_agent, cur + py_round(dt));
@@ -3298,7 +3345,7 @@ struct Eng {
   // entry); bids placed first
   DEV void mk_market_data(const Msg& m) {
     cancel_all();
-    RS A = agent_rs();
+    ARS A = agent_rs();
     const i32 nl = (i32)rs_randint(A, 1, 5);
     const i32 nb = (i32)(m.w[6] & 0xFF), na = (i32)((m.w[6] >> 8) & 0xFF);
     if (!(nb && na)) {
@@ -3363,7 +3410,7 @@ struct Eng {
   // entries and queue seqs in the loop's order
   DEV void mk_place_ladder(i64 mid, i64 spread) {
     constexpr int NL = 4 * PC.mk_depth;
-    RS A = agent_rs();
+    ARS A = agent_rs();
     i32 sz = 0;
     i64 last = 0;
     for (int i = 0; i < 2 * PC.mk_depth; i++) {
@@ -5787,6 +5834,7 @@ template <int CFG>
 struct Builder : Eng<CFG, true> {
   typedef Eng<CFG, true> E;
   typedef typename E::RS RS;
+  typedef typename E::ARS ARS;
   DEV Builder(char* e, char* lds, const RpCtx* ctx = nullptr) : E(e, lds, 0, ctx) {}
   const MmParams* mmp = nullptr;  // MXA_CFG_RMSC03_MM: this env's market-maker options
 
@@ -6377,14 +6425,14 @@ struct Builder : Eng<CFG, true> {
     // momentum size = A.randint(min, max); ZI theta = sorted(round(A.normal(0, sqrt(sigma_pv), 2 qmax)))
     for (int a = P.first_mom; a < P.first_mom + P.n_mom; a++) {
       this->rec_load(a);
-      RS A = this->agent_rs();
+      ARS A = this->agent_rs();
       this->rs(AF_SIZE, (u32)rs_randint(A, P.mom_min, P.mom_max));
       this->agent_rs_put(A);
       this->rec_store();
     }
     for (int a = P.first_mk; a < P.first_mk + P.n_mk; a++) {  // MarketMakerAgent.py:51
       this->rec_load(a);
-      RS A = this->agent_rs();
+      ARS A = this->agent_rs();
       this->rs(AF_SIZE, (u32)(i64)__builtin_rint((double)rs_randint(A, P.mk_min, P.mk_max) / 2));
       this->agent_rs_put(A);
       this->rec_store();
@@ -6394,7 +6442,7 @@ struct Builder : Eng<CFG, true> {
     for (int a = P.first_zi; a < P.first_zi + P.n_zi + P.n_hbl; a++) {  // HBL agents are ZI subclasses
       if (ZI_LANES && !zi_fallback(a)) continue;  // done by zi_theta_lanes
       this->rec_load(a);
-      RS A = this->agent_rs();
+      ARS A = this->agent_rs();
       double th[20];
       int nq = 2 * P.zi_qmax;
       for (int i = 0; i < 20; i++) th[i] = 0;
@@ -6424,7 +6472,7 @@ struct Builder : Eng<CFG, true> {
     } else {
       for (int a = 0; a < n; a++) {
         this->rec_load(a);
-        RS A = this->agent_rs();
+        ARS A = this->agent_rs();
         rs_maint(A, MXA_AGENT_LA);
         this->agent_rs_put(A);
         this->rec_store();
