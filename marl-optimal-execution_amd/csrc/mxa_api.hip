@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -28,6 +29,7 @@ extern char** environ;
 #define MXA_API_TU
 #include "mxa_kernels.hip"
 #include "mxa_entry.h"
+#include "mxa_snapshot.h"
 #ifdef MXA_ONLY_RMSC03
 #ifndef MXA_ONLY_CFG  // single-configuration variant builds (profiling): that one configuration
 #define MXA_ONLY_CFG 0
@@ -1369,6 +1371,138 @@ int mxa_policy_probe(void* stream, int32_t n, const float* x, const float* param
   p.eps = eps;
   hipLaunchKernelGGL(mxa_policy_probe_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, p, n, x, q, a);
   return hipGetLastError() == hipSuccess ? MXA_OK : MXA_EHIP;
+}
+
+// ---- env-state snapshots (include/mxa_snap.h; mxa_snapshot.h: slot layout, checks, kernel)
+}  // extern "C"
+
+struct mxa_snapshot {
+  const mxa_handle* owner = nullptr;  // compared only: a bank shared between handles is out of scope
+  int device = 0;
+  int32_t n_slots = 0, n_envs = 0;
+  // the owner's values at create: a handle that differs in one of them has other blocks or another log
+  uint64_t env_stride = 0;
+  int32_t blog_cap = 0, exlog = 0;
+  int64_t slot_bytes = 0;
+  int loads = 4;  // 16-byte loads a lane has in flight (MXA_SNAPSHOT_LOADS=8: the other instantiation)
+  std::vector<uint8_t> filled;
+  DevBuf<char> d_slots;
+  DevBuf<int32_t> d_map;
+};
+
+// everything a save / restore refuses, before any HIP call; the message goes to mxa_last_error
+static int snapshot_check(mxa_handle* h, const mxa_snapshot* s, const int32_t* map, bool save) {
+  if (!h || !s) {
+    if (h) h->err = "mxa_snapshot: null argument";
+    return MXA_EINVAL;
+  }
+  const char* what = save ? "mxa_snapshot_save: " : "mxa_snapshot_restore: ";
+  const char* why = nullptr;
+  if (s->owner != h) why = "the snapshot was created by another handle";
+  else if (s->env_stride != h->P.L.env_stride) why = "the handle's env_stride is not the snapshot's";
+  else if (s->blog_cap != h->blog_cap) why = "the book-update log was reallocated (mxa_set_book_log) after mxa_snapshot_create";
+  else if (s->exlog != h->exlog) why = "the exchange-log switch is not the one at mxa_snapshot_create";
+  else why = mxa_snap::check_map(map, h->P.n_envs, s->n_slots, save, s->filled.data());
+  if (why) {
+    h->err = std::string(what) + why;
+    return MXA_EINVAL;
+  }
+  return MXA_OK;
+}
+
+// the map to the device (as mxa_reset uploads its mask), then the one launch
+static int snapshot_copy(mxa_handle* h, const mxa_snapshot* s, const int32_t* map, int restore) {
+  const int n = h->P.n_envs;
+  std::vector<int32_t> m(n);
+  for (int i = 0; i < n; i++) m[i] = map ? map[i] : i;
+  HIPCHK(h, hipMemcpyAsync(s->d_map, m.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // m is a host temporary
+  const uint32_t nb_block = (uint32_t)mxa_snap::wg_count((int64_t)s->env_stride, s->loads);
+  const uint32_t nb_log = (uint32_t)mxa_snap::wg_count((int64_t)s->blog_cap * mxa_snap::LOG_REC_BYTES, s->loads);
+  const dim3 grid(nb_block + nb_log, (unsigned)std::min(n, 65535));
+  auto k = s->loads == 8 ? mxa_snapshot_kernel<8> : mxa_snapshot_kernel<4>;
+  return timed_launch(h, [&] {
+    hipLaunchKernelGGL(k, grid, dim3(mxa_snap::WG_LANES), 0, h->stream, (char*)h->d_env, s->env_stride,
+                       (char*)s->d_slots, (uint64_t)s->slot_bytes, (const int32_t*)s->d_map, n, (uint32_t*)h->d_built,
+                       (char*)h->d_blog.p, s->blog_cap, nb_block, restore);
+  });
+}
+
+// the copy kernel's HIP event time, once the stream is synchronised (mxa_last_kernel_ms)
+static int snapshot_ms(mxa_handle* h) {
+  float ms = 0;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->last_ms = ms;
+  return MXA_OK;
+}
+
+extern "C" {
+
+int mxa_snapshot_create(mxa_handle* h, int32_t n_slots, mxa_snapshot** out) {
+  if (!h || !out || n_slots <= 0 || !mxa_snap::stride_ok((int64_t)h->P.L.env_stride)) {
+    if (h) h->err = "mxa_snapshot_create: null argument or n_slots <= 0";
+    return MXA_EINVAL;
+  }
+  *out = nullptr;
+  ENTER(h);
+  auto s = std::make_unique<mxa_snapshot>();
+  s->owner = h;
+  s->device = h->device;
+  s->n_slots = n_slots;
+  s->n_envs = h->P.n_envs;
+  s->env_stride = h->P.L.env_stride;
+  s->blog_cap = h->d_blog ? h->blog_cap : 0;
+  s->exlog = h->exlog;
+  s->slot_bytes = mxa_snap::slot_bytes((int64_t)s->env_stride, s->blog_cap);
+  if (const char* l = getenv("MXA_SNAPSHOT_LOADS")) s->loads = atoi(l) == 8 ? 8 : 4;
+  s->filled.assign(n_slots, 0);
+  hipError_t e = s->d_slots.alloc((size_t)s->slot_bytes * n_slots);
+  if (e == hipSuccess) e = s->d_map.alloc(s->n_envs);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();  // the failed allocation is this call's error, not the next launch's
+    return hip_fail(h, e, "mxa_snapshot_create: hipMalloc");
+  }
+  *out = s.release();
+  return MXA_OK;
+}
+
+int mxa_snapshot_save(mxa_handle* h, mxa_snapshot* s, const int32_t* slot_of_env) {
+  if (int rc = snapshot_check(h, s, slot_of_env, true)) return rc;
+  ENTER(h);
+  if (int rc = snapshot_copy(h, s, slot_of_env, 0)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = snapshot_ms(h)) return rc;
+  for (int i = 0; i < h->P.n_envs; i++) {
+    const int32_t k = slot_of_env ? slot_of_env[i] : i;
+    if (k >= 0) s->filled[k] = 1;
+  }
+  return MXA_OK;
+}
+
+int mxa_snapshot_restore(mxa_handle* h, const mxa_snapshot* s, const int32_t* slot_of_env) {
+  if (int rc = snapshot_check(h, s, slot_of_env, false)) return rc;
+  ENTER(h);
+  if (int rc = snapshot_copy(h, s, slot_of_env, 1)) return rc;
+  h->started = true;  // the restored envs have popped events: the exchange log is fixed
+  // the handle's current stop time (and its exchange-log switch) hold for the restored envs
+  if (int rc = set_headers(h)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return snapshot_ms(h);
+}
+
+int mxa_snapshot_info(const mxa_snapshot* s, int64_t* out4) {
+  if (!s || !out4) return MXA_EINVAL;
+  out4[0] = s->n_slots;
+  out4[1] = s->slot_bytes;
+  out4[2] = std::count(s->filled.begin(), s->filled.end(), (uint8_t)1);
+  out4[3] = s->blog_cap > 0 ? 1 : 0;
+  return MXA_OK;
+}
+
+void mxa_snapshot_destroy(mxa_snapshot* s) {
+  if (!s) return;
+  hipSetDevice(s->device);
+  delete s;
 }
 
 }  // extern "C"

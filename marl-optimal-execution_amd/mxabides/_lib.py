@@ -151,6 +151,14 @@ BINDINGS = {
     "mxa_policy_probe": ([_P, _I32, _P, _P, _I32, _N32, _I32, _I32, _P, _P, _P, _P, _P], _I32),
 }
 EXPORTS = list(BINDINGS)
+# every export of include/mxa_snap.h (env-state snapshots; the header is a part of mxa.h's C-ABI)
+SNAPSHOT_BINDINGS = {
+    "mxa_snapshot_create": ([_P, _I32, _OUT], _I32),
+    "mxa_snapshot_save": ([_P, _P, _P], _I32),
+    "mxa_snapshot_restore": ([_P, _P, _P], _I32),
+    "mxa_snapshot_info": ([_P, _P], _I32),
+    "mxa_snapshot_destroy": ([_P], None),
+}
 COUNTER_WORDS = 34  # include/mxa.h MXA_COUNTER_WORDS
 INPLACE_WORDS = 6  # include/mxa.h MXA_INPLACE_WORDS
 RECORD_WORDS = 12  # include/mxa.h MXA_RECORD_WORDS
@@ -169,7 +177,7 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise MxaError("libmxa.so not built (%s); run __graft_entry__.build()" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in BINDINGS.items():
+    for name, (argtypes, restype) in list(BINDINGS.items()) + list(SNAPSHOT_BINDINGS.items()):
         if hasattr(L, name):  # (MXA_LIB may name a variant build that lacks some)
             f = getattr(L, name)
             f.argtypes, f.restype = argtypes, restype

@@ -72,6 +72,18 @@ class VecABIDESEnv(Handle):
         self.obs[rows] = 0
         self.flags[rows] = 0
 
+    def fork(self, src_env, envs=None):
+        """Copy env `src_env` as it stands (book, queue, RNG positions, order ids, its `obs` / `flags`
+        rows) into `envs` (default: every env) through a one-slot snapshot: the branches of a
+        what-if, e.g. every action of a table tried from one state in one step."""
+        envs = range(self.n_envs) if envs is None else envs
+        snap = self.snapshot(1)
+        try:
+            snap.save({int(src_env): 0})
+            snap.restore({int(e): 0 for e in envs})
+        finally:
+            snap.close()
+
     def set_id_persistence(self, on):
         """True (default): resets continue each env's order ids (one process); False: every
         reset starts a fresh process (ids from 0)"""

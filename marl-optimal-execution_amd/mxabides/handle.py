@@ -113,10 +113,89 @@ class Handle:
                     "mxa_read_trace")
         return buf[:n.value]
 
+    def snapshot(self, n_slots=None):
+        """A Snapshot of n_slots slots (default: one per env) on this handle's device, to save envs
+        into and restore or fork them from, mid-episode (include/mxa_snap.h)."""
+        return Snapshot(self, self.n_envs if n_slots is None else n_slots)
+
     def close(self):
         if self._h:
             self.L.mxa_destroy(self._h)
             self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Snapshot:
+    """n_slots slots of device memory, each holding one env of `handle` whole: its block, its seed
+    word and its book-update log rows (include/mxa_snap.h).  save() and restore() are one
+    kernel launch each.  `slots` says which env goes with which slot: None (env e <-> slot e), a full
+    [n_envs] map with -1 for the envs that take no part, or a dict {env: slot}.  On restore many envs
+    may name one slot (a fork); on save each slot takes one env.  On a GymKernel handle a slot also
+    keeps its env's host `obs` / `flags` rows, and restore() puts them back for the restored envs,
+    as reset(mask=...) clears exactly the masked rows."""
+
+    def __init__(self, handle, n_slots):
+        self.handle = handle
+        self.L = handle.L
+        self._s = ctypes.c_void_p()
+        handle._check(self.L.mxa_snapshot_create(handle._h, int(n_slots), ctypes.byref(self._s)), "mxa_snapshot_create")
+        self._rows = {}  # slot -> (obs row, flags word) of a GymKernel handle
+
+    def _info(self):
+        o = np.zeros(4, dtype=np.int64)
+        if self.L.mxa_snapshot_info(self._s, o.ctypes.data) < 0:
+            raise _lib.MxaError("mxa_snapshot_info failed: the snapshot is closed")
+        return o
+
+    n_slots = property(lambda self: int(self._info()[0]))
+    slot_bytes = property(lambda self: int(self._info()[1]))
+    filled = property(lambda self: int(self._info()[2]))
+    has_log = property(lambda self: bool(self._info()[3]))
+
+    def _map(self, slots):
+        """(the C-ABI's slot_of_env or None, [(env, slot)] of the envs taking part)"""
+        n = self.handle.n_envs
+        if slots is None:
+            return None, [(e, e) for e in range(n)]
+        if isinstance(slots, dict):
+            m = np.full(n, -1, dtype=np.int32)
+            for e, s in slots.items():
+                if not 0 <= int(e) < n:
+                    raise ValueError("slots: env %r outside 0 .. %d" % (e, n - 1))
+                m[int(e)] = int(s)
+        else:
+            m = np.ascontiguousarray(np.asarray(slots, dtype=np.int64).reshape(-1), dtype=np.int32)
+            if len(m) != n:
+                raise ValueError("slots: one entry per env (-1: the env takes no part)")
+        return m, [(e, int(s)) for e, s in enumerate(m) if s >= 0]
+
+    def save(self, slots=None):
+        h = self.handle
+        m, pairs = self._map(slots)
+        h._check(self.L.mxa_snapshot_save(h._h, self._s, m.ctypes.data if m is not None else None), "mxa_snapshot_save")
+        if hasattr(h, "obs"):
+            for e, s in pairs:
+                self._rows[s] = (h.obs[e].copy(), h.flags[e].copy())
+
+    def restore(self, slots=None):
+        h = self.handle
+        m, pairs = self._map(slots)
+        h._check(self.L.mxa_snapshot_restore(h._h, self._s, m.ctypes.data if m is not None else None),
+                 "mxa_snapshot_restore")
+        h._finalized = False  # mxa_finalize's results are no part of a snapshot
+        if hasattr(h, "obs"):
+            for e, s in pairs:
+                h.obs[e], h.flags[e] = self._rows[s]
+
+    def close(self):
+        if self._s:
+            self.L.mxa_snapshot_destroy(self._s)
+            self._s = ctypes.c_void_p()
 
     def __del__(self):
         try:
