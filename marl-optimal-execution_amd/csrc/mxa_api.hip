@@ -30,6 +30,7 @@ extern char** environ;
 #include "mxa_kernels.hip"
 #include "mxa_entry.h"
 #include "mxa_snapshot.h"
+#include "mxa_depth_kernels.h"
 #ifdef MXA_ONLY_RMSC03
 #ifndef MXA_ONLY_CFG  // single-configuration variant builds (profiling): that one configuration
 #define MXA_ONLY_CFG 0
@@ -1503,6 +1504,62 @@ void mxa_snapshot_destroy(mxa_snapshot* s) {
   if (!s) return;
   hipSetDevice(s->device);
   delete s;
+}
+
+}  // extern "C"
+
+// ---- book depth (include/mxa_depth.h; mxa_depth_kernels.h: the checks, the sizes and the two kernels)
+
+// everything a depth call refuses, before any HIP call; the message goes to mxa_last_error
+static int depth_check(mxa_handle* h, const char* what, int32_t levels, const void* depth) {
+  const char* why = mxa_depth::check_args(h != nullptr, depth != nullptr, levels);
+  if (!why && !h->replay && !mxa_depth::ocap_ok(h->P.L.ocap)) why = "the book has more slots than the kernel's LDS holds";
+  if (!why) return MXA_OK;
+  (h ? h->err : g_cfg_err) = std::string(what) + ": " + why;
+  return MXA_EINVAL;
+}
+
+// the one launch on the handle's stream: the ladder kernel for the replay book, else the slot kernel
+static int depth_launch(mxa_handle* h, int32_t levels, int64_t* d_depth, int32_t* d_counts) {
+  const int n = h->P.n_envs;
+  const unsigned gy = (unsigned)mxa_depth::grid_y(n);
+  if (h->replay) {
+    const RpLayout& L = h->ctx.L;
+    hipLaunchKernelGGL(mxa_depth_ladder_kernel, dim3(2, gy), dim3(mxa_depth::WAVE), 0, h->stream, (const char*)h->d_env,
+                       h->P.L.env_stride, L.off_rh, L.off_lvc, L.off_lvq, L.pmin, L.P, n, levels, (mxa_depth::Row*)d_depth,
+                       d_counts);
+  } else {
+    hipLaunchKernelGGL(mxa_depth_slots_kernel, dim3(1, gy), dim3(mxa_depth::WAVE), 0, h->stream, (const char*)h->d_env,
+                       h->P.L.env_stride, h->P.L.off_book, h->P.L.ocap, n, levels, (mxa_depth::Row*)d_depth, d_counts);
+  }
+  HIPCHK(h, hipGetLastError());
+  return MXA_OK;
+}
+
+extern "C" {
+
+int mxa_write_depth(mxa_handle* h, int32_t levels, int64_t* d_depth, int32_t* d_counts) {
+  if (int rc = depth_check(h, "mxa_write_depth", levels, d_depth)) return rc;
+  ENTER(h);
+  return depth_launch(h, levels, d_depth, d_counts);
+}
+
+int mxa_read_depth(mxa_handle* h, int32_t levels, int64_t* depth, int32_t* counts) {
+  if (int rc = depth_check(h, "mxa_read_depth", levels, depth)) return rc;
+  ENTER(h);
+  // one stream-ordered temporary: the rows, then the counts (the rows are a multiple of 16 bytes)
+  const size_t nb = (size_t)mxa_depth::depth_bytes(h->P.n_envs, levels), nc = (size_t)mxa_depth::counts_bytes(h->P.n_envs);
+  char* d = nullptr;
+  HIPCHK(h, hipMallocAsync((void**)&d, nb + nc, h->stream));
+  int rc = depth_launch(h, levels, (int64_t*)d, (int32_t*)(d + nb));
+  hipError_t e = hipSuccess;
+  if (rc == MXA_OK) e = hipMemcpyAsync(depth, d, nb, hipMemcpyDeviceToHost, h->stream);
+  if (rc == MXA_OK && e == hipSuccess && counts) e = hipMemcpyAsync(counts, d + nb, nc, hipMemcpyDeviceToHost, h->stream);
+  (void)hipFreeAsync(d, h->stream);
+  if (rc != MXA_OK) return rc;
+  HIPCHK(h, e);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MXA_OK;
 }
 
 }  // extern "C"

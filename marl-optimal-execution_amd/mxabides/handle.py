@@ -47,6 +47,14 @@ class Handle:
         cash, holdings, gain, 0), the rows bench.py all-gathers across ranks."""
         self._check(self.L.mxa_write_records(self._h, ctypes.c_void_p(device_ptr)), "mxa_write_records")
 
+    def write_depth(self, levels, depth_ptr, counts_ptr=0):
+        """Every env's top `levels` price levels into device memory, one kernel launch on the handle's
+        stream (include/mxa_depth.h mxa_write_depth): depth_ptr -> [n_envs][2][levels][2] int64, side 0
+        bids / 1 asks, row i = (price, total shares) of the i-th best level, (0, 0) from the count on;
+        counts_ptr -> [n_envs][2] int32 or 0 for none.  Returns without synchronising."""
+        self._check(self.L.mxa_write_depth(self._h, int(levels), ctypes.c_void_p(depth_ptr) if depth_ptr else None,
+                                           ctypes.c_void_p(counts_ptr) if counts_ptr else None), "mxa_write_depth")
+
     # ---- readers
     def counters(self):
         """[n_envs][COUNTER_WORDS] int64 event-class counters since the last reset (kept by
@@ -104,6 +112,24 @@ class Handle:
             else:
                 levels.append([o])
         return levels
+
+    def depth(self, levels=10):
+        """(np.int64 [n_envs, 2, levels, 2], np.int32 [n_envs, 2]): write_depth's rows and counts on the
+        host (include/mxa_depth.h mxa_read_depth; synchronises the handle's stream)"""
+        rows = np.empty((self.n_envs, 2, int(levels), 2), dtype=np.int64) if 1 <= int(levels) <= 1 << 20 else None
+        counts = np.empty((self.n_envs, 2), dtype=np.int32)
+        self._check(self.L.mxa_read_depth(self._h, int(levels), rows.ctypes.data if rows is not None else None,
+                                          counts.ctypes.data), "mxa_read_depth")
+        return rows, counts
+
+    def inside(self, env, levels):
+        """(OrderBook.getInsideBids(levels), OrderBook.getInsideAsks(levels)) of one env as the reference
+        returns them (OrderBook.py:377-398): lists of (price, quantity) tuples, best level first, as many
+        as the side has levels up to `levels`"""
+        if not 0 <= int(env) < self.n_envs:
+            raise IndexError("env %r outside 0 .. %d" % (env, self.n_envs - 1))
+        rows, counts = self.depth(levels)
+        return tuple([tuple(r) for r in rows[env, s, :counts[env, s]].tolist()] for s in (0, 1))
 
     def trace(self, env):
         """env's trace ring rows [n][10] int64 (none without a trace ring)"""
