@@ -16,7 +16,8 @@ OUT = os.path.join(HERE, "lib", "libmxa.so")
 OBJ = os.path.join(HERE, "build")
 N_CONFIGS = 18  # csrc/mxa_entry.h MXA_N_CONFIGS
 DEPS = ["mxa_api.hip", "mxa_inst.hip", "mxa_entry.h", "mxa_kernels.hip", "mxa_layout.h", "mxa_config.h", "glibc_math.h",
-        "glibc_math_tables.h", "qnet_wave_device.h", "ddqn_device.h", "mxa_snapshot.h", "mxa_depth_kernels.h"]
+        "glibc_math_tables.h", "qnet_wave_device.h", "ddqn_device.h", "mxa_snapshot.h", "mxa_depth_kernels.h",
+        "mxa_bars_kernels.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -structurizecfg-skip-uniform-regions: branches on wave-uniform conditions stay plain scalar
 # branches instead of being structurized into exec-mask regions (saveexec / restore pairs and
@@ -40,7 +41,7 @@ CFG_FLAGS = {1: ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], 2: ["-fno-slp-vect
 
 
 def sources():
-    return [os.path.join(HERE, "csrc", d) for d in DEPS] + [os.path.join(ROOT, "include", h) for h in ("mxa.h", "mxa_snap.h", "mxa_depth.h")]
+    return [os.path.join(HERE, "csrc", d) for d in DEPS] + [os.path.join(ROOT, "include", h) for h in ("mxa.h", "mxa_snap.h", "mxa_depth.h", "mxa_bars.h")]
 
 
 def build_id(extra=()):

@@ -31,6 +31,7 @@ extern char** environ;
 #include "mxa_entry.h"
 #include "mxa_snapshot.h"
 #include "mxa_depth_kernels.h"
+#include "mxa_bars_kernels.h"
 #ifdef MXA_ONLY_RMSC03
 #ifndef MXA_ONLY_CFG  // single-configuration variant builds (profiling): that one configuration
 #define MXA_ONLY_CFG 0
@@ -1559,6 +1560,82 @@ int mxa_read_depth(mxa_handle* h, int32_t levels, int64_t* depth, int32_t* count
   if (rc != MXA_OK) return rc;
   HIPCHK(h, e);
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MXA_OK;
+}
+
+}  // extern "C"
+
+// ---- time bars from the book-update log (include/mxa_bars.h; mxa_bars_kernels.h: the checks, the sizes
+// and the replay kernel)
+
+static int bars_refuse(mxa_handle* h, const char* what, const char* why) {
+  (h ? h->err : g_cfg_err) = std::string(what) + ": " + why;
+  return MXA_EINVAL;
+}
+
+// everything a bars call on a handle refuses, before any HIP call
+static int bars_check(mxa_handle* h, const char* what, int64_t t0, int64_t dt, int32_t n_bars, const void* bars) {
+  const char* why = mxa_bars::check_handle(h != nullptr, h && h->gym, h && h->d_blog && h->blog_cap > 0);
+  if (!why) why = mxa_bars::check_grid(t0, dt, n_bars, bars != nullptr, ((uintptr_t)bars & 15) == 0);
+  return why ? bars_refuse(h, what, why) : MXA_OK;
+}
+
+static hipError_t bars_launch(hipStream_t stream, const char* rec, int64_t rec_stride, int64_t rec_cap, const char* cnt0,
+                              const char* cnt1, int64_t cnt_stride, int n_envs, int32_t level_cap, int64_t t0, int64_t dt,
+                              int32_t n_bars, int64_t* d_bars, int32_t* d_status) {
+  hipLaunchKernelGGL(mxa_bars_kernel, dim3(1, (unsigned)mxa_bars::grid_y(n_envs)), dim3(mxa_bars::WAVE),
+                     (size_t)mxa_bars::lds_bytes(level_cap), stream, rec, rec_stride, rec_cap, cnt0, cnt1, cnt_stride, n_envs,
+                     level_cap, t0, dt, n_bars, d_bars, d_status);
+  return hipGetLastError();
+}
+
+// the one launch on the handle's stream: the records of d_blog, the counts from the env headers
+static int bars_launch_handle(mxa_handle* h, int64_t t0, int64_t dt, int32_t n_bars, int64_t* d_bars, int32_t* d_status) {
+  HIPCHK(h, bars_launch(h->stream, (const char*)(BlRec*)h->d_blog, (int64_t)h->blog_cap * (int64_t)sizeof(BlRec), h->blog_cap,
+                        h->d_env + offsetof(EnvHdr, blog_n), h->d_env + offsetof(EnvHdr, blog_fin),
+                        (int64_t)h->P.L.env_stride, h->P.n_envs, mxa_bars::handle_level_cap(h->replay, h->P.L.ocap), t0, dt,
+                        n_bars, d_bars, d_status));
+  return MXA_OK;
+}
+
+extern "C" {
+
+int mxa_write_bars(mxa_handle* h, int64_t t0_ns, int64_t dt_ns, int32_t n_bars, int64_t* d_bars, int32_t* d_status) {
+  if (int rc = bars_check(h, "mxa_write_bars", t0_ns, dt_ns, n_bars, d_bars)) return rc;
+  ENTER(h);
+  return bars_launch_handle(h, t0_ns, dt_ns, n_bars, d_bars, d_status);
+}
+
+int mxa_read_bars(mxa_handle* h, int64_t t0_ns, int64_t dt_ns, int32_t n_bars, int64_t* bars, int32_t* status) {
+  if (int rc = bars_check(h, "mxa_read_bars", t0_ns, dt_ns, n_bars, bars)) return rc;
+  ENTER(h);
+  // one stream-ordered temporary: the bars, then the status words (the bars are a multiple of 16 bytes)
+  const size_t nb = (size_t)mxa_bars::bars_bytes(h->P.n_envs, n_bars), ns = (size_t)mxa_bars::status_bytes(h->P.n_envs);
+  char* d = nullptr;
+  HIPCHK(h, hipMallocAsync((void**)&d, nb + ns, h->stream));
+  int rc = bars_launch_handle(h, t0_ns, dt_ns, n_bars, (int64_t*)d, (int32_t*)(d + nb));
+  hipError_t e = hipSuccess;
+  if (rc == MXA_OK) e = hipMemcpyAsync(bars, d, nb, hipMemcpyDeviceToHost, h->stream);
+  if (rc == MXA_OK && e == hipSuccess && status) e = hipMemcpyAsync(status, d + nb, ns, hipMemcpyDeviceToHost, h->stream);
+  (void)hipFreeAsync(d, h->stream);
+  if (rc != MXA_OK) return rc;
+  HIPCHK(h, e);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MXA_OK;
+}
+
+int mxa_bars_from_records(void* stream, int32_t n_envs, const mxa_book_rec* d_rec, int64_t rec_stride, const int32_t* d_count,
+                          int32_t level_cap, int64_t t0_ns, int64_t dt_ns, int32_t n_bars, int64_t* d_bars, int32_t* d_status) {
+  const char* what = "mxa_bars_from_records";
+  const char* why = mxa_bars::check_records(n_envs, d_rec != nullptr, rec_stride, d_count != nullptr, level_cap);
+  if (!why && ((uintptr_t)d_rec & 15)) why = "records not 16-byte aligned";
+  if (!why) why = mxa_bars::check_grid(t0_ns, dt_ns, n_bars, d_bars != nullptr, ((uintptr_t)d_bars & 15) == 0);
+  if (why) return bars_refuse(nullptr, what, why);
+  if (rec_stride > INT64_MAX / (int64_t)sizeof(BlRec)) return bars_refuse(nullptr, what, "rec_stride beyond int64 bytes");
+  const hipError_t e = bars_launch((hipStream_t)stream, (const char*)d_rec, rec_stride * (int64_t)sizeof(BlRec), rec_stride,
+                                   (const char*)d_count, (const char*)d_count, sizeof(int32_t), n_envs, level_cap, t0_ns, dt_ns,
+                                   n_bars, d_bars, d_status);
+  if (e != hipSuccess) return hip_fail(nullptr, e, what);
   return MXA_OK;
 }
 

@@ -302,6 +302,27 @@ class VecMarket(Handle):
                                 % (env, n.value, self.book_log_cap))
         return buf[:min(n.value, self.book_log_cap)]
 
+    def write_bars(self, t0_ns, dt_ns, n_bars, bars_ptr, status_ptr=0):
+        """Every env's time bars from its book-update log into device memory, one kernel launch on the
+        handle's stream (include/mxa_bars.h mxa_write_bars; mxabides.bars has the columns): bars_ptr ->
+        [n_envs][n_bars][12] int64, bar i covering [t0_ns + i * dt_ns, t0_ns + (i + 1) * dt_ns);
+        status_ptr -> [n_envs][4] int32 or 0 for none.  It sees the records written so far and returns
+        without synchronising."""
+        self._check(self.L.mxa_write_bars(self._h, int(t0_ns), int(dt_ns), int(n_bars),
+                                          ctypes.c_void_p(bars_ptr) if bars_ptr else None,
+                                          ctypes.c_void_p(status_ptr) if status_ptr else None), "mxa_write_bars")
+
+    def bars(self, t0_ns, dt_ns, n_bars):
+        """(np.int64 [n_envs, n_bars, 12], np.int32 [n_envs, 4]): write_bars' bars and status words on the
+        host (include/mxa_bars.h mxa_read_bars; synchronises the handle's stream)"""
+        if not self.book_log_cap:
+            raise ValueError("created with book_log=0")
+        out = np.empty((self.n_envs, int(n_bars), 12), dtype=np.int64) if 1 <= int(n_bars) <= 1 << 24 else None
+        status = np.empty((self.n_envs, 4), dtype=np.int32)
+        self._check(self.L.mxa_read_bars(self._h, int(t0_ns), int(dt_ns), int(n_bars),
+                                         out.ctypes.data if out is not None else None, status.ctypes.data), "mxa_read_bars")
+        return out, status
+
     def book_log_rows(self, env):
         """OrderBook.book_log of env as flat rows (mxabides.booklog format: t, n, executed qty,
         average price, n (price, volume) pairs)"""
