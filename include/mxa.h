@@ -241,6 +241,10 @@ int mxa_run_until(mxa_handle* h, int64_t t_stop_ns, int64_t* events_out);
  * ValueAgent.py:66-86), observing the oracle in agent order.  Idempotent (state is not saved);
  * plain Kernel.runner configs only (MXA_EINVAL for GymKernel handles). */
 int mxa_finalize(mxa_handle* h);
+/* The readers.  Every mxa_read_* (those of mxa_depth.h and mxa_bars.h too) copies on the handle's
+ * stream: it is ordered after all work submitted to that stream before it (mxa_launch, mxa_step_device,
+ * mxa_step_many, mxa_step_policy, every mxa_write_*), whether the stream is the handle's own or a
+ * caller's (mxa_set_stream), and it returns with that stream idle.  No mxa_sync is needed in front. */
 /* env's rows of the last mxa_finalize, one per agent (row 0, the exchange, is empty) */
 int mxa_read_final(mxa_handle* h, int32_t env, mxa_agent_final* out, int32_t cap);
 int mxa_read_summary(mxa_handle* h, mxa_env_summary* out /* [n_envs] */);
@@ -298,7 +302,9 @@ int64_t mxa_env_bytes(const mxa_handle* h);
 int mxa_set_stream(mxa_handle* h, void* stream);
 /* HIP event timing of the last mxa_run / mxa_launch sequence, milliseconds */
 double mxa_last_kernel_ms(const mxa_handle* h);
-const char* mxa_last_error(const mxa_handle* h); /* NULL: the last mxa_config_* / mxa_create_config error */
+/* NULL: the last error of a call without a handle (mxa_config_*, mxa_create_config, mxa_bars_from_records, or a
+ * refusal of a null handle).  A refusal "with a message" reads "<function>: <reason>". */
+const char* mxa_last_error(const mxa_handle* h);
 void mxa_destroy(mxa_handle* h);
 
 /* ABIDESEnv on a replay tape: n_rec time-sorted records (ns since midnight, order id > 0,

@@ -52,7 +52,8 @@ typedef struct mxa_handle mxa_handle;
  * mxa_write_bars is one kernel launch, asynchronous on the handle's stream like mxa_write_depth: it
  * reads each env's record count from the env header on the device, so between two launches
  * mid-episode it sees the records so far, and it returns without synchronising.  mxa_read_bars is the
- * same into HOST arrays (a stream-ordered temporary, a copy, one synchronise).  Both work on every
+ * same into HOST arrays under the readers' contract of mxa.h (a stream-ordered temporary, freed on every
+ * return path, a copy, one synchronise).  Both work on every
  * handle that carries a book-update log: Kernel.runner handles, the replay runner and the TWAP
  * handles.  level_cap is MXA_BAR_MAX_LEVELS on the replay handles, else the book capacity rounded up
  * to 64 and capped at MXA_BAR_MAX_LEVELS (live levels never exceed resting orders).

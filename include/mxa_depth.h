@@ -21,8 +21,9 @@ typedef struct mxa_handle mxa_handle;
  * call writes nothing outside the two arrays.
  * mxa_write_depth is one kernel launch, asynchronous on the handle's stream like mxa_write_records:
  * it sees the books as the last launch queued before it leaves them and returns without
- * synchronising.  mxa_read_depth is the same into HOST arrays: a stream-ordered temporary and a copy
- * on the handle's stream, the way mxa_read_counters works, and then it synchronises.
+ * synchronising.  mxa_read_depth is the same into HOST arrays under the readers' contract of mxa.h:
+ * a stream-ordered temporary (freed on every return path) and a copy on the handle's stream, the way
+ * mxa_read_counters works, and then it synchronises.
  * Every handle kind holds one exchange book, so both work on all of them: Kernel.runner handles
  * (mxa_create, _hist, _params, _config), GymKernel handles (rmsc03 + DummyRL, the replay), the replay
  * runner and the TWAP handles.  An env that has finished, errored or never run reports the book that

@@ -31,7 +31,8 @@ typedef struct mxa_handle mxa_handle;
  * mxa_set_stop_time holds for restored envs, and the handle counts as started (mxa_set_exchange_log).
  * mxa_finalize's results are no part of a snapshot (finalize again); the seeds of the next
  * mxa_reset and the market-maker options are untouched.
- * MXA_EINVAL, with a message in mxa_last_error and before any HIP call: null arguments, n_slots <= 0,
+ * MXA_EINVAL, with a message in mxa_last_error (of the handle; of NULL when the handle is the null
+ * argument) and before any HIP call: null arguments, n_slots <= 0,
  * a map entry < -1 or >= n_slots, a NULL map with too few slots, two envs saving to one slot,
  * restoring a slot never saved, a snapshot created by another handle, a handle whose env bytes,
  * log capacity (mxa_set_book_log reallocates the log) or exchange-log switch differ from those at

@@ -300,6 +300,46 @@ static int hip_fail(mxa_handle* h, hipError_t e, const char* what) {
 // every entry point that works on a handle's device starts here: the caller's current device may differ
 #define ENTER(h) HIPCHK(h, hipSetDevice(h->device))
 
+static std::string g_cfg_err;  // mxa_last_error(NULL): the last error of a call without a handle
+
+// the one refusal, before any HIP call: "what: why" for mxa_last_error (of the handle, or of NULL)
+static int refuse(mxa_handle* h, const char* what, const char* why) {
+  (h ? h->err : g_cfg_err) = std::string(what) + ": " + why;
+  return MXA_EINVAL;
+}
+
+// the one device-to-host path of a handle: copies on its stream, so behind everything submitted to it
+// before, and finish() is the wait after the copies a reader can size (include/mxa.h, the readers)
+static hipError_t dev_read(mxa_handle* h, const void* src, size_t bytes, void* dst) {
+  return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+}
+// `bytes` at `offset` of one env's block
+static hipError_t env_read(mxa_handle* h, int32_t env, uint64_t offset, size_t bytes, void* dst) {
+  return dev_read(h, h->d_env + (size_t)env * h->P.L.env_stride + offset, bytes, dst);
+}
+// the same field of every env, packed: dst [n_envs][bytes]
+static hipError_t env_read_all(mxa_handle* h, uint64_t offset, size_t bytes, void* dst) {
+  return hipMemcpy2DAsync(dst, bytes, h->d_env + offset, h->P.L.env_stride, bytes, h->P.n_envs, hipMemcpyDeviceToHost,
+                          h->stream);
+}
+static hipError_t finish(mxa_handle* h) { return hipStreamSynchronize(h->stream); }
+
+// a stream-ordered temporary, freed on its stream on every return path
+struct StreamTmp {
+  char* p = nullptr;
+  hipStream_t stream = nullptr;
+  StreamTmp() = default;
+  StreamTmp(const StreamTmp&) = delete;
+  StreamTmp& operator=(const StreamTmp&) = delete;
+  ~StreamTmp() {
+    if (p) (void)hipFreeAsync(p, stream);
+  }
+  hipError_t alloc(size_t bytes, hipStream_t s) {
+    stream = s;
+    return hipMallocAsync((void**)&p, bytes, s);
+  }
+};
+
 // pops a step launch may take: a step ends at its own time (GymKernel.stepRunner), never at this
 static constexpr int64_t STEP_POPS = (int64_t)1 << 40;
 
@@ -377,7 +417,7 @@ static int create_common(std::unique_ptr<mxa_handle> owned, const uint32_t* seed
     HIPCHK(h, h->d_act.alloc(3 * (size_t)n_envs));
     HIPCHK(h, h->d_obs.alloc(9 * (size_t)n_envs));
     HIPCHK(h, h->d_flags.alloc(n_envs));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, finish(h));
   }
   const int rc = mxa_reset(h, nullptr);  // a fresh process: ids from 0
   h->persist_ids = h->gym;               // later resets continue the process (Order.py:8-9)
@@ -393,10 +433,21 @@ static int timed_launch(mxa_handle* h, Launch launch) {
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   return MXA_OK;
 }
+// the time of the last timed_launch, once the stream is synchronised: added to *sum, or (no sum) what
+// mxa_last_kernel_ms returns
+static int launch_ms(mxa_handle* h, float* sum = nullptr) {
+  float ms = 0;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  if (sum) *sum += ms;
+  else h->last_ms = ms;
+  return MXA_OK;
+}
 
-// a step launch of a GymKernel handle: the arguments every step launcher starts with, then `tail`
+// a step launch of a GymKernel handle: the arguments every step launcher starts with, then `tail`.
+// A null launcher (a library built without the step kernels, a configuration without this one) refuses
 template <class F, class... Tail>
 static int step_launch(mxa_handle* h, F instr, F fast, Tail... tail) {
+  if (!instr) return MXA_EINVAL;
   ENTER(h);
   return timed_launch(h, [&] {
     h->pick(instr, fast)(dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, h->P.n_envs,
@@ -506,7 +557,7 @@ int mxa_set_mm_params(mxa_handle* h, const mxa_mm_params* per_env) {
   ENTER(h);
   memcpy(h->mm.data(), per_env, sizeof(MmParams) * h->P.n_envs);
   HIPCHK(h, hipMemcpyAsync(h->d_mmp, h->mm.data(), sizeof(MmParams) * h->P.n_envs, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -551,8 +602,6 @@ int mxa_create_hist(int32_t config, int32_t n_envs, const uint32_t* seeds, int32
 #ifndef MXA_JIT_CFG_FLAGS
 #define MXA_JIT_CFG_FLAGS ""
 #endif
-static std::string g_cfg_err;  // mxa_last_error(NULL): the last composition error
-
 static int cfg_fail(const std::string& what) {
   g_cfg_err = what;
   return MXA_EINVAL;
@@ -612,7 +661,7 @@ int mxa_config_key(const mxa_config* cfg, char* out17) {
 
 int mxa_config_capacities(const mxa_config* cfg, int32_t out2[2]) {
   if (!cfg || !out2) return cfg_fail("mxa_config_capacities: bad arguments");
-  if (const char* why = mxa_cfg::custom_check(*cfg)) return cfg_fail(std::string("mxa_config_capacities: ") + why);
+  if (const char* why = mxa_cfg::custom_check(*cfg)) return refuse(nullptr, "mxa_config_capacities", why);
   const mxa_cfg::Shape S = mxa_cfg::custom_shape(*cfg);
   out2[0] = S.sq * 64;
   out2[1] = S.so * 64;
@@ -621,7 +670,7 @@ int mxa_config_capacities(const mxa_config* cfg, int32_t out2[2]) {
 
 int mxa_config_compile(const mxa_config* cfg, const char* cache_dir, char* path_out, int32_t path_cap) {
   if (!cfg) return cfg_fail("mxa_config_compile: null composition");
-  if (const char* why = mxa_cfg::custom_check(*cfg)) return cfg_fail(std::string("mxa_config_compile: ") + why);
+  if (const char* why = mxa_cfg::custom_check(*cfg)) return refuse(nullptr, "mxa_config_compile", why);
   const std::string key = cfg_key(*cfg), dir = cfg_dir(cache_dir), so = cfg_lib(cache_dir, key);
   if (path_out && path_cap > 0) snprintf(path_out, path_cap, "%s", so.c_str());
   struct stat st{};
@@ -684,7 +733,7 @@ typedef int (*mxa_custom_entry_fn)(MxaEntry*, MxaParams*, size_t*, mxa_config*, 
 int mxa_create_config(const mxa_config* cfg, int32_t n_envs, const uint32_t* seeds, int32_t device, int32_t trace_cap,
                       const char* cache_dir, mxa_handle** out) {
   if (!out || n_envs <= 0 || !seeds || trace_cap < 0 || !cfg) return cfg_fail("mxa_create_config: bad arguments");
-  if (const char* why = mxa_cfg::custom_check(*cfg)) return cfg_fail(std::string("mxa_create_config: ") + why);
+  if (const char* why = mxa_cfg::custom_check(*cfg)) return refuse(nullptr, "mxa_create_config", why);
   const std::string key = cfg_key(*cfg), so = cfg_lib(cache_dir, key);
   static std::mutex mu;
   static std::map<std::string, void*> loaded;  // specialisations stay loaded: their kernels are registered
@@ -760,9 +809,6 @@ static int create_replay(int cfg, const int64_t* t, const int64_t* oid, const in
                          const int8_t* buy, int32_t n_rec, int32_t n_envs, int32_t device, int32_t trace_cap,
                          mxa_handle** out, int32_t twap_trade) {
   if (!out || !t || !oid || !price || !size || !buy || n_rec <= 0 || n_envs <= 0 || trace_cap < 0) return MXA_EINVAL;
-#ifdef MXA_NO_GYM
-  return MXA_EINVAL;
-#else
   int64_t pmin = INT64_MAX, pmax = INT64_MIN, min_id = INT64_MAX;
   int n_zero = 0;  // ORDER_ID 0 records: LimitOrder(order_id=0) takes an auto id (Order.py:26)
   for (int i = 0; i < n_rec; i++) {
@@ -847,38 +893,26 @@ static int create_replay(int cfg, const int64_t* t, const int64_t* oid, const in
   h->tape.add(c.ufirst, ufirst.data(), ufirst.size(), 4);
   std::vector<uint32_t> seeds(n_envs, 0u);  // nothing in this composition draws
   return create_common(std::move(h), seeds.data(), device, out);
-#endif
 }
 
 // ABIDESEnv.step for every env: actions [n][3] -> obs [n][9], flags [n] (all host arrays)
 int mxa_step(mxa_handle* h, const double* actions, double* obs, int32_t* flags) {
   if (!h || !h->gym || !actions || !obs || !flags) return MXA_EINVAL;
-#ifdef MXA_NO_GYM
-  return MXA_EINVAL;
-#else
   ENTER(h);
   int n = h->P.n_envs;
   HIPCHK(h, hipMemcpyAsync(h->d_act, actions, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
   int rc = mxa_step_device(h, h->d_act, h->d_obs, h->d_flags);
   if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(obs, h->d_obs, sizeof(double) * 9 * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(flags, h->d_flags, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->last_ms = ms;
-  return MXA_OK;
-#endif
+  HIPCHK(h, dev_read(h, h->d_obs, sizeof(double) * 9 * n, obs));
+  HIPCHK(h, dev_read(h, h->d_flags, sizeof(int32_t) * n, flags));
+  HIPCHK(h, finish(h));
+  return launch_ms(h);
 }
 
 // k consecutive steps in one launch, device arrays: actions [k][n][3] -> obs [k][n][9], flags [k][n]
 int mxa_step_many(mxa_handle* h, int32_t k, const double* d_actions, double* d_obs, int32_t* d_flags) {
   if (!h || !h->gym || k <= 0 || !d_actions || !d_obs || !d_flags) return MXA_EINVAL;
-#ifdef MXA_NO_GYM
-  return MXA_EINVAL;
-#else
   return step_launch(h, h->e.step_many, h->e.step_many_fast, d_actions, d_obs, d_flags, (int)k);
-#endif
 }
 
 // k periods in one launch with the epsilon-greedy Q-network policy evaluated in the step kernel
@@ -890,23 +924,14 @@ int mxa_step_policy(mxa_handle* h, int32_t k, int32_t first_zero, const mxa_poli
   if (!p->test && (!p->u || !p->rnd || !p->eps)) return MXA_EINVAL;
   if (!qwave::dims_ok(p->n_layers, p->dims) || p->dims[0] != 2) return MXA_EINVAL;
   if (d_state && h->P.n_rl != 1) return MXA_EINVAL;  // the rl-state row is the one execution agent's
-#ifdef MXA_NO_GYM
-  return MXA_EINVAL;
-#else
-  if (!h->e.step_policy) return MXA_EINVAL;
   return step_launch(h, h->e.step_policy, h->e.step_policy_fast, *p, d_obs, d_flags, d_a, d_act, d_state, (int)k,
                      (int)(first_zero != 0));
-#endif
 }
 
 // the same with device arrays (e.g. torch tensors), asynchronous on the handle's stream
 int mxa_step_device(mxa_handle* h, const double* d_actions, double* d_obs, int32_t* d_flags) {
   if (!h || !h->gym) return MXA_EINVAL;
-#ifdef MXA_NO_GYM
-  return MXA_EINVAL;
-#else
   return step_launch(h, h->e.step, h->e.step_fast, d_actions, d_obs, d_flags);
-#endif
 }
 
 int mxa_reset(mxa_handle* h, const uint8_t* mask) {
@@ -920,7 +945,7 @@ int mxa_reset(mxa_handle* h, const uint8_t* mask) {
     std::vector<uint8_t> m(n);
     for (int i = 0; i < n; i++) m[i] = (!mask || mask[i]) ? on : 0;
     HIPCHK(h, hipMemcpyAsync(h->d_mask, m.data(), n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // m is a host temporary
+    HIPCHK(h, finish(h));  // m is a host temporary
     dm = h->d_mask;
   }
   h->e.build(dim3(n), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride, n, h->d_seeds, dm, h->d_ctx);
@@ -932,7 +957,7 @@ int mxa_reset(mxa_handle* h, const uint8_t* mask) {
   // the build cleared the header: the exchange-log switch and the stopTime override outlive resets
   if (h->exlog || h->t_stop > 0)
     if (int rc = set_headers(h)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -941,7 +966,7 @@ int mxa_set_stop_time(mxa_handle* h, int64_t t_stop_ns) {
   ENTER(h);
   h->t_stop = t_stop_ns > 0 ? t_stop_ns : 0;
   if (int rc = set_headers(h)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -978,7 +1003,7 @@ int mxa_launch(mxa_handle* h, int64_t max_pops) {
 int mxa_sync(mxa_handle* h) {
   if (!h) return MXA_EINVAL;
   ENTER(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -994,8 +1019,8 @@ int mxa_run(mxa_handle* h, int64_t chunk, int32_t max_launches, int32_t* launche
     hipLaunchKernelGGL(mxa_compact_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_env, h->P.L.env_stride, n,
                        h->d_list, h->d_count);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(&running, h->d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, dev_read(h, h->d_count, sizeof(int), &running));
+    HIPCHK(h, finish(h));
     if (running < 0 || running > n) {
       h->err = "mxa_run: running-env count out of range";
       return MXA_EHIP;
@@ -1015,9 +1040,7 @@ int mxa_run(mxa_handle* h, int64_t chunk, int32_t max_launches, int32_t* launche
     if (rc != MXA_OK) return rc;
     launches++;
     if ((rc = compact(running)) != MXA_OK) return rc;
-    float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    total += ms;
+    if ((rc = launch_ms(h, &total)) != MXA_OK) return rc;
     pops = chunk;  // mxa_set_launch_schedule: the first launch only is first_chunk
   }
   h->last_ms = total;
@@ -1037,7 +1060,7 @@ int mxa_set_book_log(mxa_handle* h, int32_t cap) {
   // Kernel.runner handles, the replay's (config/marketreplay.py) included; not GymKernel handles
   if (!h || h->gym || !h->e.run_log || cap < 0) return MXA_EINVAL;
   ENTER(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   h->d_blog.free();
   h->blog_cap = 0;
   if (cap > 0) {
@@ -1048,7 +1071,7 @@ int mxa_set_book_log(mxa_handle* h, int32_t cap) {
                              h->stream));
   HIPCHK(h, hipMemset2DAsync(h->d_env + offsetof(EnvHdr, blog_fin), h->P.L.env_stride, 0, sizeof(int32_t),
                              h->P.n_envs, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -1057,16 +1080,14 @@ int mxa_set_book_log(mxa_handle* h, int32_t cap) {
 int mxa_set_exchange_log(mxa_handle* h, int32_t on) {
   if (!h || h->gym || !h->e.run_log || on < 0 || on > 1) return MXA_EINVAL;
   if (on && !h->d_blog) return MXA_EINVAL;  // it rides in the book-update log: mxa_set_book_log first
-  if (h->started && on != h->exlog) {
-    // placements logged before the switch would be missing from the log (its order rows name
-    // them), and a log switched off mid-run ends without its tail: set it before the run
-    h->err = "mxa_set_exchange_log: set it before the first launch (or after a whole-handle mxa_reset)";
-    return MXA_EINVAL;
-  }
+  // placements logged before the switch would be missing from the log (its order rows name
+  // them), and a log switched off mid-run ends without its tail: set it before the run
+  if (h->started && on != h->exlog)
+    return refuse(h, "mxa_set_exchange_log", "set it before the first launch (or after a whole-handle mxa_reset)");
   ENTER(h);
   h->exlog = on;
   if (int rc = set_headers(h)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -1080,18 +1101,15 @@ int mxa_read_book_log(mxa_handle* h, int32_t env, mxa_book_rec* out, int64_t cap
                 "exchange-log record codes");
   ENTER(h);
   EnvHdr hd;
-  HIPCHK(h, hipMemcpyAsync(&hd, h->d_env + (size_t)env * h->P.L.env_stride, sizeof(hd), hipMemcpyDeviceToHost,
-                           h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, env_read(h, env, 0, sizeof hd, &hd));
+  HIPCHK(h, finish(h));  // the header sizes the second copy
   // after a kernelStopping pass: its oracle observations follow the run's records
   int64_t cnt = h->d_blog ? (hd.blog_fin > hd.blog_n ? hd.blog_fin : hd.blog_n) : 0;
   *n = cnt;  // beyond the capacity: the log overflowed (the first `blog_cap` records are kept)
   if (cnt > h->blog_cap) cnt = h->blog_cap;
   const int64_t m = cnt < cap ? cnt : cap;
-  if (m > 0)
-    HIPCHK(h, hipMemcpyAsync(out, h->d_blog + (size_t)env * h->blog_cap, sizeof(BlRec) * m, hipMemcpyDeviceToHost,
-                             h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (m > 0) HIPCHK(h, dev_read(h, h->d_blog + (size_t)env * h->blog_cap, sizeof(BlRec) * m, out));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -1103,16 +1121,15 @@ int mxa_finalize(mxa_handle* h) {
   (h->d_blog ? h->e.stop_log : h->e.stop)(dim3(h->P.n_envs), dim3(64), h->lds, h->stream, h->d_env, h->P.L.env_stride,
                                           h->P.n_envs, h->d_final, h->d_blog, h->blog_cap, h->d_ctx);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
 int mxa_read_final(mxa_handle* h, int32_t env, mxa_agent_final* out, int32_t cap) {
   if (!h || !h->d_final || env < 0 || env >= h->P.n_envs || !out || cap < h->P.n_agents) return MXA_EINVAL;
   ENTER(h);
-  HIPCHK(h, hipMemcpyAsync(out, h->d_final + (size_t)env * h->P.n_agents, sizeof(mxa_agent_final) * h->P.n_agents,
-                           hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, dev_read(h, h->d_final + (size_t)env * h->P.n_agents, sizeof(mxa_agent_final) * h->P.n_agents, out));
+  HIPCHK(h, finish(h));
   return h->P.n_agents;
 }
 
@@ -1121,9 +1138,8 @@ int mxa_read_summary(mxa_handle* h, mxa_env_summary* out) {
   ENTER(h);
   int n = h->P.n_envs;
   std::vector<EnvHdr> hd(n);
-  HIPCHK(h, hipMemcpy2DAsync(hd.data(), sizeof(EnvHdr), h->d_env, h->P.L.env_stride, sizeof(EnvHdr), n,
-                             hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, env_read_all(h, 0, sizeof(EnvHdr), hd.data()));
+  HIPCHK(h, finish(h));
   for (int i = 0; i < n; i++) {
     out[i].status = hd[i].status;
     out[i].err = hd[i].err;
@@ -1143,8 +1159,11 @@ int mxa_read_agents(mxa_handle* h, int32_t env, mxa_agent_state* out, int32_t ca
   ENTER(h);
   int n = std::min(cap, h->P.n_agents);
   std::vector<uint32_t> rec((size_t)h->P.n_agents * MXA_AGENT_WORDS);
-  HIPCHK(h, hipMemcpy(rec.data(), h->d_env + (size_t)env * h->P.L.env_stride + h->P.L.off_ag, rec.size() * 4,
-                      hipMemcpyDeviceToHost));
+  std::vector<RpOrder> mo(h->replay ? h->ctx.L.D : 0);  // MarketReplayAgent.orders lives in the dense table
+  HIPCHK(h, env_read(h, env, h->P.L.off_ag, rec.size() * 4, rec.data()));
+  HIPCHK(h, env_read(h, env, h->ctx.L.off_mro, sizeof(RpOrder) * mo.size(), mo.data()));
+  HIPCHK(h, finish(h));
+  const int32_t mo_open = (int32_t)std::count_if(mo.begin(), mo.end(), [](const RpOrder& o) { return o.present != 0; });
   for (int a = 0; a < n; a++) {
     const uint32_t* r = &rec[(size_t)a * MXA_AGENT_WORDS];
     auto g64 = [&](int f) { return (int64_t)(((uint64_t)r[f + 1] << 32) | r[f]); };
@@ -1155,14 +1174,7 @@ int mxa_read_agents(mxa_handle* h, int32_t env, mxa_agent_state* out, int32_t ca
     out[a].type = (int32_t)r[AF_TYPE];
     out[a].flags = (int32_t)r[AF_FLAGS];
     out[a].starting_cash = g64(AF_START_CASH);
-    if (h->replay && out[a].type == AG_REPLAY) {  // MarketReplayAgent.orders lives in the dense table
-      std::vector<RpOrder> mo(h->ctx.L.D);
-      HIPCHK(h, hipMemcpy(mo.data(), h->d_env + (size_t)env * h->P.L.env_stride + h->ctx.L.off_mro,
-                          sizeof(RpOrder) * mo.size(), hipMemcpyDeviceToHost));
-      int64_t c = 0;
-      for (auto& o : mo) c += o.present ? 1 : 0;
-      out[a].n_open = c;
-    }
+    if (h->replay && out[a].type == AG_REPLAY) out[a].n_open = mo_open;
   }
   return n;
 }
@@ -1172,12 +1184,12 @@ int mxa_read_book(mxa_handle* h, int32_t env, int32_t side, int64_t* out4, int32
   ENTER(h);
   if (h->replay) {  // price ladder: levels best-first, FIFO lists
     const RpLayout& L = h->ctx.L;
-    char* e = h->d_env + (size_t)env * h->P.L.env_stride;
     std::vector<int32_t> cnt(L.P), head(L.P);
     std::vector<RpEntry> pool(L.C);
-    HIPCHK(h, hipMemcpy(cnt.data(), e + L.off_lvc + 4ull * side * L.P, 4ull * L.P, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(head.data(), e + L.off_lvh + 4ull * side * L.P, 4ull * L.P, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(pool.data(), e + L.off_pool, sizeof(RpEntry) * L.C, hipMemcpyDeviceToHost));
+    HIPCHK(h, env_read(h, env, L.off_lvc + 4ull * side * L.P, 4ull * L.P, cnt.data()));
+    HIPCHK(h, env_read(h, env, L.off_lvh + 4ull * side * L.P, 4ull * L.P, head.data()));
+    HIPCHK(h, env_read(h, env, L.off_pool, sizeof(RpEntry) * L.C, pool.data()));
+    HIPCHK(h, finish(h));
     int n = 0;
     for (int k = 0; k < L.P; k++) {
       int x = side == 0 ? L.P - 1 - k : k;
@@ -1196,8 +1208,8 @@ int mxa_read_book(mxa_handle* h, int32_t env, int32_t side, int64_t* out4, int32
   }
   int oc = h->P.L.ocap;
   std::vector<SavedOrder> so(oc);
-  HIPCHK(h, hipMemcpy(so.data(), h->d_env + (size_t)env * h->P.L.env_stride + h->P.L.off_book,
-                      sizeof(SavedOrder) * oc, hipMemcpyDeviceToHost));
+  HIPCHK(h, env_read(h, env, h->P.L.off_book, sizeof(SavedOrder) * oc, so.data()));
+  HIPCHK(h, finish(h));
   std::vector<SavedOrder> v;
   int buy = side == 0 ? 1 : 0;
   for (auto& o : so)
@@ -1219,10 +1231,11 @@ int mxa_read_trace(mxa_handle* h, int32_t env, int64_t* out, int64_t cap, int64_
   if (!h || env < 0 || env >= h->P.n_envs) return MXA_ERANGE;
   ENTER(h);
   EnvHdr hd;
-  char* e = h->d_env + (size_t)env * h->P.L.env_stride;
-  HIPCHK(h, hipMemcpy(&hd, e, sizeof hd, hipMemcpyDeviceToHost));
+  HIPCHK(h, env_read(h, env, 0, sizeof hd, &hd));
+  HIPCHK(h, finish(h));  // the header sizes the second copy
   int64_t n = std::min<int64_t>(std::min<int64_t>(hd.trace_len, h->P.L.trace_cap), cap);
-  if (n > 0) HIPCHK(h, hipMemcpy(out, e + h->P.L.off_trace, (size_t)n * MXA_TRACE_ROW_BYTES, hipMemcpyDeviceToHost));
+  if (n > 0) HIPCHK(h, env_read(h, env, h->P.L.off_trace, (size_t)n * MXA_TRACE_ROW_BYTES, out));
+  HIPCHK(h, finish(h));
   if (nout) *nout = n;
   return MXA_OK;
 }
@@ -1231,7 +1244,7 @@ int mxa_set_seeds(mxa_handle* h, const uint32_t* seeds) {
   if (!h || !seeds) return MXA_EINVAL;
   ENTER(h);
   HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, sizeof(uint32_t) * h->P.n_envs, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -1261,21 +1274,21 @@ int mxa_read_counters(mxa_handle* h, int64_t* out) {
   if (!h || !out) return MXA_EINVAL;
   ENTER(h);
   const int n = h->P.n_envs;
-  int64_t* d = nullptr;
-  HIPCHK(h, hipMallocAsync((void**)&d, sizeof(int64_t) * MXA_COUNTER_WORDS * n, h->stream));
+  const size_t bytes = sizeof(int64_t) * MXA_COUNTER_WORDS * n;
+  StreamTmp d;
+  HIPCHK(h, d.alloc(bytes, h->stream));
   hipLaunchKernelGGL(mxa_counters_kernel, dim3(n), dim3(64), 0, h->stream, h->d_env, h->P.L.env_stride, n, h->P.L.off_ag,
-                     h->P.n_agents, d);
+                     h->P.n_agents, (int64_t*)d.p);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(out, d, sizeof(int64_t) * MXA_COUNTER_WORDS * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipFreeAsync(d, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, dev_read(h, d.p, bytes, out));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
 int mxa_read_inplace(mxa_handle* h, uint64_t* out) {
   if (!h || !out || !h->e.inplace) return MXA_EINVAL;
   ENTER(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, finish(h));
   return h->e.inplace(out) ? MXA_EHIP : MXA_OK;
 }
 
@@ -1300,8 +1313,8 @@ int mxa_read_raw(mxa_handle* h, int32_t env, int64_t offset, int64_t bytes, void
   if (!h || env < 0 || env >= h->P.n_envs || offset < 0 || bytes < 0 || offset + bytes > (int64_t)h->P.L.env_stride)
     return MXA_ERANGE;
   ENTER(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy(out, h->d_env + (size_t)env * h->P.L.env_stride + offset, bytes, hipMemcpyDeviceToHost));
+  HIPCHK(h, env_read(h, env, offset, bytes, out));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -1349,8 +1362,9 @@ int mxa_math_probe(int32_t device, int32_t mode, const double* x, const double* 
   DevBuf<double> dx, dy, dout;
   size_t bytes = sizeof(double) * n;
   if (dx.alloc(n) != hipSuccess || dy.alloc(n) != hipSuccess || dout.alloc(n) != hipSuccess) return MXA_ENOMEM;
-  hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
-  hipMemcpy(dy, y ? y : x, bytes, hipMemcpyHostToDevice);
+  if (hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(dy, y ? y : x, bytes, hipMemcpyHostToDevice) != hipSuccess)
+    return MXA_EHIP;
   hipLaunchKernelGGL(mxa_math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, mode, dx.p, dy.p, dout.p,
                      n);
   if (hipGetLastError() != hipSuccess) return MXA_EHIP;
@@ -1394,22 +1408,14 @@ struct mxa_snapshot {
 
 // everything a save / restore refuses, before any HIP call; the message goes to mxa_last_error
 static int snapshot_check(mxa_handle* h, const mxa_snapshot* s, const int32_t* map, bool save) {
-  if (!h || !s) {
-    if (h) h->err = "mxa_snapshot: null argument";
-    return MXA_EINVAL;
-  }
-  const char* what = save ? "mxa_snapshot_save: " : "mxa_snapshot_restore: ";
+  if (!h || !s) return refuse(h, "mxa_snapshot", "null argument");
   const char* why = nullptr;
   if (s->owner != h) why = "the snapshot was created by another handle";
   else if (s->env_stride != h->P.L.env_stride) why = "the handle's env_stride is not the snapshot's";
   else if (s->blog_cap != h->blog_cap) why = "the book-update log was reallocated (mxa_set_book_log) after mxa_snapshot_create";
   else if (s->exlog != h->exlog) why = "the exchange-log switch is not the one at mxa_snapshot_create";
   else why = mxa_snap::check_map(map, h->P.n_envs, s->n_slots, save, s->filled.data());
-  if (why) {
-    h->err = std::string(what) + why;
-    return MXA_EINVAL;
-  }
-  return MXA_OK;
+  return why ? refuse(h, save ? "mxa_snapshot_save" : "mxa_snapshot_restore", why) : MXA_OK;
 }
 
 // the map to the device (as mxa_reset uploads its mask), then the one launch
@@ -1418,7 +1424,7 @@ static int snapshot_copy(mxa_handle* h, const mxa_snapshot* s, const int32_t* ma
   std::vector<int32_t> m(n);
   for (int i = 0; i < n; i++) m[i] = map ? map[i] : i;
   HIPCHK(h, hipMemcpyAsync(s->d_map, m.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));  // m is a host temporary
+  HIPCHK(h, finish(h));  // m is a host temporary
   const uint32_t nb_block = (uint32_t)mxa_snap::wg_count((int64_t)s->env_stride, s->loads);
   const uint32_t nb_log = (uint32_t)mxa_snap::wg_count((int64_t)s->blog_cap * mxa_snap::LOG_REC_BYTES, s->loads);
   const dim3 grid(nb_block + nb_log, (unsigned)std::min(n, 65535));
@@ -1430,21 +1436,11 @@ static int snapshot_copy(mxa_handle* h, const mxa_snapshot* s, const int32_t* ma
   });
 }
 
-// the copy kernel's HIP event time, once the stream is synchronised (mxa_last_kernel_ms)
-static int snapshot_ms(mxa_handle* h) {
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->last_ms = ms;
-  return MXA_OK;
-}
-
 extern "C" {
 
 int mxa_snapshot_create(mxa_handle* h, int32_t n_slots, mxa_snapshot** out) {
-  if (!h || !out || n_slots <= 0 || !mxa_snap::stride_ok((int64_t)h->P.L.env_stride)) {
-    if (h) h->err = "mxa_snapshot_create: null argument or n_slots <= 0";
-    return MXA_EINVAL;
-  }
+  if (!h || !out || n_slots <= 0 || !mxa_snap::stride_ok((int64_t)h->P.L.env_stride))
+    return refuse(h, "mxa_snapshot_create", "null argument or n_slots <= 0");
   *out = nullptr;
   ENTER(h);
   auto s = std::make_unique<mxa_snapshot>();
@@ -1472,8 +1468,8 @@ int mxa_snapshot_save(mxa_handle* h, mxa_snapshot* s, const int32_t* slot_of_env
   if (int rc = snapshot_check(h, s, slot_of_env, true)) return rc;
   ENTER(h);
   if (int rc = snapshot_copy(h, s, slot_of_env, 0)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (int rc = snapshot_ms(h)) return rc;
+  HIPCHK(h, finish(h));
+  if (int rc = launch_ms(h)) return rc;
   for (int i = 0; i < h->P.n_envs; i++) {
     const int32_t k = slot_of_env ? slot_of_env[i] : i;
     if (k >= 0) s->filled[k] = 1;
@@ -1488,8 +1484,8 @@ int mxa_snapshot_restore(mxa_handle* h, const mxa_snapshot* s, const int32_t* sl
   h->started = true;  // the restored envs have popped events: the exchange log is fixed
   // the handle's current stop time (and its exchange-log switch) hold for the restored envs
   if (int rc = set_headers(h)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return snapshot_ms(h);
+  HIPCHK(h, finish(h));
+  return launch_ms(h);
 }
 
 int mxa_snapshot_info(const mxa_snapshot* s, int64_t* out4) {
@@ -1515,9 +1511,7 @@ void mxa_snapshot_destroy(mxa_snapshot* s) {
 static int depth_check(mxa_handle* h, const char* what, int32_t levels, const void* depth) {
   const char* why = mxa_depth::check_args(h != nullptr, depth != nullptr, levels);
   if (!why && !h->replay && !mxa_depth::ocap_ok(h->P.L.ocap)) why = "the book has more slots than the kernel's LDS holds";
-  if (!why) return MXA_OK;
-  (h ? h->err : g_cfg_err) = std::string(what) + ": " + why;
-  return MXA_EINVAL;
+  return why ? refuse(h, what, why) : MXA_OK;
 }
 
 // the one launch on the handle's stream: the ladder kernel for the replay book, else the slot kernel
@@ -1550,16 +1544,12 @@ int mxa_read_depth(mxa_handle* h, int32_t levels, int64_t* depth, int32_t* count
   ENTER(h);
   // one stream-ordered temporary: the rows, then the counts (the rows are a multiple of 16 bytes)
   const size_t nb = (size_t)mxa_depth::depth_bytes(h->P.n_envs, levels), nc = (size_t)mxa_depth::counts_bytes(h->P.n_envs);
-  char* d = nullptr;
-  HIPCHK(h, hipMallocAsync((void**)&d, nb + nc, h->stream));
-  int rc = depth_launch(h, levels, (int64_t*)d, (int32_t*)(d + nb));
-  hipError_t e = hipSuccess;
-  if (rc == MXA_OK) e = hipMemcpyAsync(depth, d, nb, hipMemcpyDeviceToHost, h->stream);
-  if (rc == MXA_OK && e == hipSuccess && counts) e = hipMemcpyAsync(counts, d + nb, nc, hipMemcpyDeviceToHost, h->stream);
-  (void)hipFreeAsync(d, h->stream);
-  if (rc != MXA_OK) return rc;
-  HIPCHK(h, e);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  StreamTmp d;
+  HIPCHK(h, d.alloc(nb + nc, h->stream));
+  if (int rc = depth_launch(h, levels, (int64_t*)d.p, (int32_t*)(d.p + nb))) return rc;
+  HIPCHK(h, dev_read(h, d.p, nb, depth));
+  if (counts) HIPCHK(h, dev_read(h, d.p + nb, nc, counts));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -1568,16 +1558,11 @@ int mxa_read_depth(mxa_handle* h, int32_t levels, int64_t* depth, int32_t* count
 // ---- time bars from the book-update log (include/mxa_bars.h; mxa_bars_kernels.h: the checks, the sizes
 // and the replay kernel)
 
-static int bars_refuse(mxa_handle* h, const char* what, const char* why) {
-  (h ? h->err : g_cfg_err) = std::string(what) + ": " + why;
-  return MXA_EINVAL;
-}
-
 // everything a bars call on a handle refuses, before any HIP call
 static int bars_check(mxa_handle* h, const char* what, int64_t t0, int64_t dt, int32_t n_bars, const void* bars) {
   const char* why = mxa_bars::check_handle(h != nullptr, h && h->gym, h && h->d_blog && h->blog_cap > 0);
   if (!why) why = mxa_bars::check_grid(t0, dt, n_bars, bars != nullptr, ((uintptr_t)bars & 15) == 0);
-  return why ? bars_refuse(h, what, why) : MXA_OK;
+  return why ? refuse(h, what, why) : MXA_OK;
 }
 
 static hipError_t bars_launch(hipStream_t stream, const char* rec, int64_t rec_stride, int64_t rec_cap, const char* cnt0,
@@ -1611,16 +1596,12 @@ int mxa_read_bars(mxa_handle* h, int64_t t0_ns, int64_t dt_ns, int32_t n_bars, i
   ENTER(h);
   // one stream-ordered temporary: the bars, then the status words (the bars are a multiple of 16 bytes)
   const size_t nb = (size_t)mxa_bars::bars_bytes(h->P.n_envs, n_bars), ns = (size_t)mxa_bars::status_bytes(h->P.n_envs);
-  char* d = nullptr;
-  HIPCHK(h, hipMallocAsync((void**)&d, nb + ns, h->stream));
-  int rc = bars_launch_handle(h, t0_ns, dt_ns, n_bars, (int64_t*)d, (int32_t*)(d + nb));
-  hipError_t e = hipSuccess;
-  if (rc == MXA_OK) e = hipMemcpyAsync(bars, d, nb, hipMemcpyDeviceToHost, h->stream);
-  if (rc == MXA_OK && e == hipSuccess && status) e = hipMemcpyAsync(status, d + nb, ns, hipMemcpyDeviceToHost, h->stream);
-  (void)hipFreeAsync(d, h->stream);
-  if (rc != MXA_OK) return rc;
-  HIPCHK(h, e);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  StreamTmp d;
+  HIPCHK(h, d.alloc(nb + ns, h->stream));
+  if (int rc = bars_launch_handle(h, t0_ns, dt_ns, n_bars, (int64_t*)d.p, (int32_t*)(d.p + nb))) return rc;
+  HIPCHK(h, dev_read(h, d.p, nb, bars));
+  if (status) HIPCHK(h, dev_read(h, d.p + nb, ns, status));
+  HIPCHK(h, finish(h));
   return MXA_OK;
 }
 
@@ -1630,8 +1611,8 @@ int mxa_bars_from_records(void* stream, int32_t n_envs, const mxa_book_rec* d_re
   const char* why = mxa_bars::check_records(n_envs, d_rec != nullptr, rec_stride, d_count != nullptr, level_cap);
   if (!why && ((uintptr_t)d_rec & 15)) why = "records not 16-byte aligned";
   if (!why) why = mxa_bars::check_grid(t0_ns, dt_ns, n_bars, d_bars != nullptr, ((uintptr_t)d_bars & 15) == 0);
-  if (why) return bars_refuse(nullptr, what, why);
-  if (rec_stride > INT64_MAX / (int64_t)sizeof(BlRec)) return bars_refuse(nullptr, what, "rec_stride beyond int64 bytes");
+  if (!why && rec_stride > INT64_MAX / (int64_t)sizeof(BlRec)) why = "rec_stride beyond int64 bytes";
+  if (why) return refuse(nullptr, what, why);
   const hipError_t e = bars_launch((hipStream_t)stream, (const char*)d_rec, rec_stride * (int64_t)sizeof(BlRec), rec_stride,
                                    (const char*)d_count, (const char*)d_count, sizeof(int32_t), n_envs, level_cap, t0_ns, dt_ns,
                                    n_bars, d_bars, d_status);
