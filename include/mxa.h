@@ -127,8 +127,13 @@ mxa_mm_params mxa_mm_defaults(void);
  * config must be MXA_RMSC03; the handle's instantiation (MXA_RMSC03_MM) reads the options from the
  * market maker's record and holds 320 pending events, 192 resting orders and 256 open orders per
  * agent (scripts/rmsc03.sh's 50 ticks peak at 266 / 122 / 204); beyond that an env stops with a
- * capacity error, never silently.  MXA_EINVAL for options the script cannot run (negative
- * window or ticks, wake-up period <= 0). */
+ * capacity error, never silently.  The largest ladder it holds is --mm-num-ticks 63: 128 orders,
+ * placed while the previous 128 are still open, fill the open-order list exactly (peaks 314 / 144 /
+ * 256); from 64 ticks on an env stops at its second quote with error 3 (the open-order list), a
+ * ladder too long for the book at its first with error 2.  A
+ * ladder price beyond the 32-bit order words (mid + window + ticks > INT32_MAX) stops the env with
+ * error 31 at that requote, never a wrapped price.  MXA_EINVAL for options the script cannot run
+ * (negative window or ticks, wake-up period <= 0). */
 int mxa_create_params(int32_t config, int32_t n_envs, const uint32_t* seeds, const mxa_mm_params* per_env,
                       int32_t device, int32_t trace_cap, mxa_handle** out);
 /* A Kernel.runner composition given at run time (SURVEY.md §8(b) "mxa_config"): the agent list a

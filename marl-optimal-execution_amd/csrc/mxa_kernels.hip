@@ -3113,6 +3113,13 @@ struct Eng {
   // with both replies in: cancel every open order, place the ladder around the mid, sleep a period
   DEV void mm_requote(i64 mid) {
     if (!fl(FL_AW_SPREAD) && !fl(FL_AW_TV)) {
+      if constexpr (PC.mm_rt) {  // the order words are 32-bit: stop loudly, never wrap a ladder price
+        const i64 t = mm_ticks();
+        if (MXA_UNLIKELY(mid + mm_window() + t > INT32_MAX || mid - 1 - t < INT32_MIN)) {
+          fail(ERR_ORDER_PRICE);
+          return;
+        }
+      }
       cancel_all();
       const i64 ticks = mm_ticks();
       i64 hb = mid - 1, la = mid + mm_window();

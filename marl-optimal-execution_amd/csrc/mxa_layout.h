@@ -98,7 +98,11 @@ enum {
   // marketreplay / ABIDESEnv: a QUERY_SPREAD reply whose best level's total quantity is beyond the
   // reply's signed 32-bit quantity word (the ladder keeps 64-bit totals; the reference quotes a
   // Python int)
-  ERR_RP_QUOTE_SIZE = 30
+  ERR_RP_QUOTE_SIZE = 30,
+  // a limit price beyond the device's 32-bit order words (POVMarketMakerAgent with per-env options:
+  // mid + --mm-window-size + --mm-num-ticks past INT32_MAX); the reference's Python int has no
+  // bound, so the env stops at that requote
+  ERR_ORDER_PRICE = 31
 };
 
 // per-env scalar header (first bytes of the env block)

@@ -54,7 +54,8 @@ ERR_NAMES = {0: "none", 1: "event queue capacity", 2: "order book capacity", 3: 
              27: "ExecutionAgent.placeOrders: placeMarketOrder at horizon[-2] (not restated)",
              28: "SpreadBasedMarketMakerAgent: mid unbound (UnboundLocalError)",
              29: "order quantity beyond the device's 32-bit order words (POVMarketMakerAgent pov x volume)",
-             30: "replay QUERY_SPREAD: a best level's total quantity beyond the reply's signed 32-bit word"}
+             30: "replay QUERY_SPREAD: a best level's total quantity beyond the reply's signed 32-bit word",
+             31: "market-maker ladder price beyond the 32-bit order words (mid + --mm-window-size + --mm-num-ticks)"}
 
 
 class EnvSummary(ctypes.Structure):

@@ -352,7 +352,8 @@ struct ora_env {
     char sym[16]; /* the report's symbol when set (ora_set_symbol): -t/--ticker of replay configs */
     int64_t st_max_heap, st_max_resting, st_max_open, st_resting, st_max_hist_tx;
     /* the device's per-env capacities (ora_set_capacities; 0: unbounded, the reference's own) */
-    int64_t cap_q, cap_b;
+    int64_t cap_q, cap_b, cap_open;
+    int price_words; /* ora_set_price_words: the device's 32-bit limit prices */
     char* report;
     int64_t report_len;
     /* Kernel.summaryLog: (agent, event type, int or float value) rows */
@@ -1278,6 +1279,10 @@ static void get_tv(ora_env* e, agent_t* a, int64_t lookback) {
 static void place_limit(ora_env* e, agent_t* a, int64_t qty, int is_buy, int64_t price) {
     int64_t oid = next_order_id(e);
     if (qty > 0) {
+        if (e->cap_open > 0 && a->nord >= e->cap_open) { /* one open order more than the device's list holds */
+            fail(e, ORA_ERR_OPEN_FULL, "open-order list over the device's capacity (ora_set_open_capacity)");
+            return;
+        }
         if (a->nord == a->capord) {
             a->capord = a->capord ? 2 * a->capord : 8;
             a->ord = (aord_t*)realloc(a->ord, sizeof(aord_t) * a->capord);
@@ -1663,9 +1668,13 @@ static void mm_receive(ora_env* e, agent_t* a, const msg_t* m) {
         }
     }
     if (!a->aw_spread && !a->aw_tv) {
-        cancel_all(e, a);
         int64_t hb = mid - 1, la = mid + a->window;
         int64_t lb = hb - a->num_ticks, ha = la + a->num_ticks;
+        if (e->price_words && (ha > INT32_MAX || lb < INT32_MIN)) { /* a ladder price the device cannot carry */
+            fail(e, ORA_ERR_ORDER_PRICE, "market-maker ladder price beyond the device's 32-bit words (ora_set_price_words)");
+            return;
+        }
+        cancel_all(e, a);
         for (int64_t p = lb; p <= hb; p++) place_limit(e, a, a->order_size, 1, p);
         for (int64_t p = la; p <= ha; p++) place_limit(e, a, a->order_size, 0, p);
         a->aw_spread = a->aw_tv = 1;
@@ -1807,6 +1816,10 @@ static void mk_receive(ora_env* e, agent_t* a, const msg_t* m) {
 /* placeLimitOrder(..., order_id=<the ladder's id>) (TradingAgent.py:309-349) */
 static void place_limit_id(ora_env* e, agent_t* a, int64_t qty, int is_buy, int64_t price, int64_t oid) {
     if (qty <= 0) return;
+    if (e->cap_open > 0 && a->nord >= e->cap_open) {
+        fail(e, ORA_ERR_OPEN_FULL, "open-order list over the device's capacity (ora_set_open_capacity)");
+        return;
+    }
     if (a->nord == a->capord) {
         a->capord = a->capord ? 2 * a->capord : 8;
         a->ord = (aord_t*)realloc(a->ord, sizeof(aord_t) * a->capord);
@@ -3576,6 +3589,13 @@ void ora_set_capacities(ora_env* e, int64_t q, int64_t b) {
     if (q > 0 && e->nheap > q) fail(e, ORA_ERR_QUEUE_FULL, "event queue over the device's capacity at construction");
     if (b > 0 && e->st_resting > b) fail(e, ORA_ERR_BOOK_FULL, "order book over the device's capacity at construction");
 }
+/* the device's open-order list (include/mxa.h: 256 per agent) as every agent's own: the
+ * placeLimitOrder with a quantity > 0 of an agent that already holds n open orders fails the env;
+ * the order id is consumed, nothing is sent, the handler runs on.  0 leaves it unbounded. */
+void ora_set_open_capacity(ora_env* e, int64_t n) { e->cap_open = n; }
+/* the device's 32-bit limit-price words: the market maker's requote whose ladder would hold a
+ * price outside int32 fails the env before it cancels or places anything */
+void ora_set_price_words(ora_env* e, int on) { e->price_words = on; }
 void ora_stats(const ora_env* e, int64_t* out) {
     out[0] = e->st_max_heap;
     out[1] = e->st_max_resting;
@@ -3606,6 +3626,8 @@ typedef struct {
     const ora_mm_params* mm; /* optional: rmsc03 with per-env market-maker options */
     const ora_config* cfg;   /* optional: a runtime composition */
     int64_t cap_q, cap_b;    /* optional: ora_set_capacities of every env */
+    int64_t cap_open;        /* optional: ora_set_open_capacity of every env */
+    int price_words;         /* optional: ora_set_price_words of every env */
     pthread_mutex_t mu;
     int rc;
 } batch_t;
@@ -3624,6 +3646,8 @@ static void* batch_worker(void* p) {
             continue;
         }
         if (b->cap_q > 0 || b->cap_b > 0) ora_set_capacities(e, b->cap_q, b->cap_b);
+        if (b->cap_open > 0) ora_set_open_capacity(e, b->cap_open);
+        if (b->price_words) ora_set_price_words(e, 1);
         ora_run(e, b->max_pops);
         b->ev[i] = e->pops;
         b->h[i] = e->hash;
@@ -3637,9 +3661,11 @@ static void* batch_worker(void* p) {
 static int run_batch_impl(const char* config, const uint32_t* seeds, int n, int threads, int64_t max_pops,
                           int64_t* events_out, uint64_t* hash_out, int32_t* err_out, int64_t* stats_out,
                           double* seconds_out, const ora_mm_params* mm, const ora_config* cfg, int64_t cap_q,
-                          int64_t cap_b) {
+                          int64_t cap_b, int64_t cap_open) {
     batch_t b;
     memset(&b, 0, sizeof b);
+    b.cap_open = cap_open & ~(1LL << 62); /* bit 62: ora_set_price_words (ora_run_batch_mm_cap) */
+    b.price_words = (int)((cap_open >> 62) & 1);
     b.cap_q = cap_q;
     b.cap_b = cap_b;
     b.mm = mm;
@@ -3668,20 +3694,20 @@ static int run_batch_impl(const char* config, const uint32_t* seeds, int n, int 
 
 int ora_run_batch(const char* config, const uint32_t* seeds, int n, int threads, int64_t max_pops,
                   int64_t* events_out, uint64_t* hash_out, double* seconds_out) {
-    return run_batch_impl(config, seeds, n, threads, max_pops, events_out, hash_out, NULL, NULL, seconds_out, NULL, NULL, 0, 0);
+    return run_batch_impl(config, seeds, n, threads, max_pops, events_out, hash_out, NULL, NULL, seconds_out, NULL, NULL, 0, 0, 0);
 }
 
 /* the same, with each env's error code (ora_error) in err_out[n] */
 int ora_run_batch_err(const char* config, const uint32_t* seeds, int n, int threads, int64_t max_pops,
                       int64_t* events_out, uint64_t* hash_out, int32_t* err_out, double* seconds_out) {
-    return run_batch_impl(config, seeds, n, threads, max_pops, events_out, hash_out, err_out, NULL, seconds_out, NULL, NULL, 0, 0);
+    return run_batch_impl(config, seeds, n, threads, max_pops, events_out, hash_out, err_out, NULL, seconds_out, NULL, NULL, 0, 0, 0);
 }
 
 /* capacity statistics (ora_stats) of n envs: stats_out[n][4] */
 int ora_run_batch_stats(const char* config, const uint32_t* seeds, int n, int threads, int64_t* stats_out) {
     int64_t* ev = (int64_t*)calloc(n, sizeof(int64_t));
     uint64_t* h = (uint64_t*)calloc(n, sizeof(uint64_t));
-    int rc = run_batch_impl(config, seeds, n, threads, -1, ev, h, NULL, stats_out, NULL, NULL, NULL, 0, 0);
+    int rc = run_batch_impl(config, seeds, n, threads, -1, ev, h, NULL, stats_out, NULL, NULL, NULL, 0, 0, 0);
     free(ev);
     free(h);
     return rc;
@@ -3691,19 +3717,26 @@ int ora_run_batch_config(const ora_config* c, const uint32_t* seeds, int n, int 
                          int64_t* events_out, uint64_t* hash_out, int32_t* err_out, int64_t* stats_out,
                          double* seconds_out) {
     return run_batch_impl("composition", seeds, n, threads, max_pops, events_out, hash_out, err_out, stats_out,
-                          seconds_out, NULL, c, 0, 0);
+                          seconds_out, NULL, c, 0, 0, 0);
 }
 int ora_run_batch_config_cap(const ora_config* c, int64_t q, int64_t b, const uint32_t* seeds, int n, int threads,
                              int64_t max_pops, int64_t* events_out, uint64_t* hash_out, int32_t* err_out,
                              int64_t* stats_out, double* seconds_out) {
     return run_batch_impl("composition", seeds, n, threads, max_pops, events_out, hash_out, err_out, stats_out,
-                          seconds_out, NULL, c, q, b);
+                          seconds_out, NULL, c, q, b, 0);
 }
 int ora_run_batch_mm(const uint32_t* seeds, const ora_mm_params* params, int n, int threads, int64_t max_pops,
                      int64_t* events_out, uint64_t* hash_out, int32_t* err_out, int64_t* stats_out, double* seconds_out) {
     if (!params) return -1;
     return run_batch_impl("rmsc03", seeds, n, threads, max_pops, events_out, hash_out, err_out, stats_out, seconds_out,
-                          params, NULL, 0, 0);
+                          params, NULL, 0, 0, 0);
+}
+int ora_run_batch_mm_cap(const uint32_t* seeds, const ora_mm_params* params, int64_t q, int64_t b, int64_t open,
+                         int price_words, int n, int threads, int64_t max_pops, int64_t* events_out, uint64_t* hash_out, int32_t* err_out,
+                         int64_t* stats_out, double* seconds_out) {
+    if (!params) return -1;
+    return run_batch_impl("rmsc03", seeds, n, threads, max_pops, events_out, hash_out, err_out, stats_out, seconds_out,
+                          params, NULL, q, b, open | ((int64_t)(price_words != 0) << 62));
 }
 
 void ora_set_book_log(ora_env* e, int on) {

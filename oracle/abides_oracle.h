@@ -81,6 +81,15 @@ void ora_stats(const ora_env* e, int64_t* out);
 #define ORA_ERR_QUEUE_FULL (-20)
 #define ORA_ERR_BOOK_FULL (-21)
 void ora_set_capacities(ora_env* e, int64_t q, int64_t b);
+/* Opt-in, beside it: the device's open-order list (n per agent; 0 = unbounded).  A placeLimitOrder
+ * with a quantity > 0 of an agent that already holds n open orders fails the env the same way. */
+#define ORA_ERR_OPEN_FULL (-22)
+void ora_set_open_capacity(ora_env* e, int64_t n);
+/* Opt-in: the device's 32-bit limit-price words.  The POV market maker's requote whose ladder
+ * would hold a price outside int32 (a huge --mm-window-size) fails the env in that pop, before it
+ * cancels or places anything; the reference's Python int would carry the price. */
+#define ORA_ERR_ORDER_PRICE (-23)
+void ora_set_price_words(ora_env* e, int on);
 /* Kernel.summaryLog after ora_finish: (agent, type 0 STARTING_CASH / 1 FINAL_CASH_POSITION /
  * 2 ENDING_CASH / 3 FINAL_VALUATION, is-float, int value, float value); returns the row count */
 const char* ora_agent_type_name(const ora_env* e, int id); /* Agent.type (the summary's AgentStrategy) */
@@ -128,6 +137,11 @@ int ora_create_mm(uint32_t seed, const ora_mm_params* p, ora_env** out);
 /* ora_run_batch_err / _stats of rmsc03 envs with per-env market-maker options params[n] */
 int ora_run_batch_mm(const uint32_t* seeds, const ora_mm_params* params, int n, int threads, int64_t max_pops,
                      int64_t* events_out, uint64_t* hash_out, int32_t* err_out, int64_t* stats_out, double* seconds_out);
+/* the same with ora_set_capacities(env, q, b), ora_set_open_capacity(env, open) and
+ * ora_set_price_words(env, price_words) on every env */
+int ora_run_batch_mm_cap(const uint32_t* seeds, const ora_mm_params* params, int64_t q, int64_t b, int64_t open,
+                         int price_words, int n, int threads, int64_t max_pops, int64_t* events_out, uint64_t* hash_out, int32_t* err_out,
+                         int64_t* stats_out, double* seconds_out);
 /* runtime compositions (include/mxa.h mxa_config, the same layout): a base script's construction
  * ("rmsc03", "value_noise", "sparse_zi_100", "sparse_zi_1000") with the caller's agent counts,
  * per-class parameters and session.  rmsc03, random_fund_value, value_noise and sparse_zi_* are

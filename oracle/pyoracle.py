@@ -17,6 +17,10 @@ _lib = None
 _fund_set = False
 # ora_set_capacities' fail() codes (abides_oracle.h)
 ERR_QUEUE_FULL, ERR_BOOK_FULL = -20, -21
+# ora_set_open_capacity's
+ERR_OPEN_FULL = -22
+# ora_set_price_words'
+ERR_ORDER_PRICE = -23
 
 
 def _ensure_fundamental(config):
@@ -168,7 +172,8 @@ class OracleEnv:
     MM_DTYPE record) runs config/rmsc03.py with those --mm-* options; a composition (an
     OraConfig, or a MarketConfig's bytes) runs ora_create_config.  capacities=(q, b) makes the
     device's per-env capacities the env's own (ora_set_capacities): the push or enterOrder that
-    would exceed one fails the env with ERR_QUEUE_FULL / ERR_BOOK_FULL."""
+    would exceed one fails the env with ERR_QUEUE_FULL / ERR_BOOK_FULL.  A third entry, (q, b, open),
+    is the per-agent open-order list's (set_open_capacity)."""
 
     def __init__(self, config, seed, trace_cap=0, mm=None, capacities=None):
         L = lib()
@@ -198,6 +203,25 @@ class OracleEnv:
             L.ora_set_capacities.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
             L.ora_set_capacities.restype = None
             L.ora_set_capacities(self._h, int(capacities[0]), int(capacities[1]))
+            if len(capacities) > 2:
+                self.set_open_capacity(capacities[2])
+
+    def set_open_capacity(self, n):
+        """the device's open-order list as every agent's own (ora_set_open_capacity): the
+        placeLimitOrder of an agent that already holds n open orders fails the env with
+        ERR_OPEN_FULL; before run()"""
+        L = lib()
+        L.ora_set_open_capacity.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+        L.ora_set_open_capacity.restype = None
+        L.ora_set_open_capacity(self._h, int(n))
+
+    def set_price_words(self, on=True):
+        """the device's 32-bit limit-price words (ora_set_price_words): a market-maker ladder with a
+        price outside int32 fails the env with ERR_ORDER_PRICE; before run()"""
+        L = lib()
+        L.ora_set_price_words.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.ora_set_price_words.restype = None
+        L.ora_set_price_words(self._h, 1 if on else 0)
 
     def run(self, max_pops=-1):
         return lib().ora_run(self._h, max_pops)
@@ -408,10 +432,14 @@ def run_batch_config(cfg, seeds, threads, max_pops=-1, stats=False, capacities=N
     return (ev, hs, er, sec.value, st) if stats else (ev, hs, er, sec.value)
 
 
-def run_batch_mm(seeds, params, threads, max_pops=-1, stats=False):
+def run_batch_mm(seeds, params, threads, max_pops=-1, stats=False, capacities=None, price_words=False):
     """rmsc03 envs with per-env market-maker options (params: MM_DTYPE [n]): events, hashes, error
-    codes, seconds (and the [n][4] capacity statistics with stats=True)"""
+    codes, seconds (and the [n][4] capacity statistics with stats=True); capacities=(q, b, open):
+    every env under ora_set_capacities and ora_set_open_capacity (0: that one unbounded);
+    price_words: every env under ora_set_price_words"""
     L = lib()
+    L.ora_run_batch_mm_cap.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int64] * 3 + \
+        [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_double)]
     L.ora_run_batch_mm.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + \
         [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_double)]
     seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
@@ -424,8 +452,14 @@ def run_batch_mm(seeds, params, threads, max_pops=-1, stats=False):
     er = np.zeros(n, dtype=np.int32)
     st = np.zeros((n, 4), dtype=np.int64)
     sec = ctypes.c_double()
-    if L.ora_run_batch_mm(seeds.ctypes.data, prm.ctypes.data, n, threads, max_pops, ev.ctypes.data, hs.ctypes.data,
-                          er.ctypes.data, st.ctypes.data if stats else None, ctypes.byref(sec)):
+    if capacities is not None or price_words:
+        q, b, op = (int(x) for x in (capacities or (0, 0, 0)))
+        rc = L.ora_run_batch_mm_cap(seeds.ctypes.data, prm.ctypes.data, q, b, op, 1 if price_words else 0, n, threads, max_pops, ev.ctypes.data,
+                                    hs.ctypes.data, er.ctypes.data, st.ctypes.data if stats else None, ctypes.byref(sec))
+    else:
+        rc = L.ora_run_batch_mm(seeds.ctypes.data, prm.ctypes.data, n, threads, max_pops, ev.ctypes.data, hs.ctypes.data,
+                                er.ctypes.data, st.ctypes.data if stats else None, ctypes.byref(sec))
+    if rc:
         raise RuntimeError("oracle batch failed")
     return (ev, hs, er, sec.value, st) if stats else (ev, hs, er, sec.value)
 

@@ -13,8 +13,9 @@ from golden_util import GOLDEN
 # "b" resting orders)
 POOLS = {"cap_zi95_q": (2048, "q"), "cap_zi95_b": (2048, "b"), "cap_zi95_qb": (2048, "qb"),
          "cap_zi384_q": (512, "q"), "cap_zi767_q": (512, "q"), "cap_rmsc03_q": (2048, "q")}
-# the oracle's fail() codes of ora_set_capacities -> the device's ERR_QUEUE_FULL / ERR_BOOK_FULL
-ORACLE_TO_DEVICE = {pyoracle.ERR_QUEUE_FULL: 1, pyoracle.ERR_BOOK_FULL: 2}
+# the oracle's fail() codes of ora_set_capacities / ora_set_open_capacity -> the device's
+# ERR_QUEUE_FULL / ERR_BOOK_FULL / ERR_OPEN_FULL
+ORACLE_TO_DEVICE = {pyoracle.ERR_QUEUE_FULL: 1, pyoracle.ERR_BOOK_FULL: 2, pyoracle.ERR_OPEN_FULL: 3}
 THREADS = min(16, os.cpu_count() or 1)
 
 

@@ -223,6 +223,7 @@ class CompactBookLog(list):
         t = int(row["QuoteTime"].value)
         super().append((t, [(int(q), int(v)) for q, v in row.items() if q != "QuoteTime" and v != 0]))
 SUMMARY_ONLY = False
+PACKED = False  # one <name>.npz holding trace, final state and summary log (the market maker's option edges)
 
 
 def install_stubs():
@@ -438,6 +439,10 @@ def run_config(cfg, seed, out, full, composition=None):
     summary = [{"AgentID": int(r["AgentID"]), "AgentStrategy": r["AgentStrategy"], "EventType": r["EventType"],
                 "Event": r["Event"] if isinstance(r["Event"], (int, float)) else str(r["Event"])}
                for r in kern.summaryLog]
+    if PACKED:  # one file: the trace kept, the final state and the summary log as JSON text
+        np.savez_compressed(out + ".npz", trace=tr if full else tr[:20000], final=np.array(json.dumps(final)),
+                            summary=np.array(json.dumps(summary)))
+        return
     with open(out + "_summary.json", "w") as f:
         json.dump(summary, f, indent=0)
     if FLOG:  # the oracle's f_log[sym] after kernelStopping (ExchangeAgent.kernelTerminating's frame)
@@ -645,7 +650,9 @@ def main():
     global BOOK_LOG
     global FLOG
     global EXLOG
+    global PACKED
     if sys.argv[1] == "run":
+        PACKED = "--packed" in sys.argv
         SUMMARY_ONLY = "--summary-only" in sys.argv
         BOOK_LOG = "--booklog" in sys.argv
         FLOG = "--flog" in sys.argv
@@ -721,13 +728,24 @@ def main():
             # config/rmsc03.py with the market-maker options of scripts/rmsc03.sh (pov 0.05, min
             # order size 25, window 5, 50 ticks, wake-up "10S"), on the script's seeds 30-35
             ] + [("rmsc03%0.05,25,5,50,10S", s, s == 30) for s in range(30, 36)]
+    # the option edges of the market maker (tests/mm_edge_util.py), each one packed file (--packed;
+    # golden_util.load_named reads both forms): order size 0; py_round ties at window 0 with the
+    # 128-order ladder that fills the device's open-order list; 66 orders (a second batched pass
+    # of 2); a ladder of 2 at the mid; a period longer than the session; a sub-second period; 130
+    # orders, beyond the device's list (oracle only)
+    packed = [("rmsc03%0,0,5,20,1S", 30, False), ("rmsc03%0.5,1,0,63,1S", 30, False),
+              ("rmsc03%0.05,20,5,32,1S", 31, False), ("rmsc03%0.05,20,0,0,1S", 33, False),
+              ("rmsc03%0.05,20,5,20,7H", 30, False), ("rmsc03%0.05,20,5,20,500ms", 31, False),
+              ("rmsc03%0.05,20,5,64,1S", 31, False)]
+    jobs += packed
     if len(sys.argv) > 2:
         jobs = [j for j in jobs if j[0] == sys.argv[2] or j[0].startswith(sys.argv[2] + ":")]
     procs = []
     for cfg, seed, full in jobs:
         out = os.path.join(HERE, "%s_%d" % (cfg.replace("@", "_stop").replace(":", ""), seed) if "@" in cfg
                            else "%s_%d" % (cfg.replace(":", "_").replace("%", "_mm_").replace(",", "_"), seed))
-        cmd = [sys.executable, os.path.abspath(__file__), "run", cfg, str(seed), out] + (["--full"] if full else []) + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "run", cfg, str(seed), out] + (["--full"] if full else []) + extra \
+            + (["--packed"] if (cfg, seed, full) in packed else [])
         wd = tempfile.mkdtemp(prefix="gf_")
         procs.append((cfg, seed, subprocess.Popen(cmd, cwd=wd, env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))))
     for cfg, seed, p in procs:

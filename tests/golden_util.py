@@ -64,7 +64,11 @@ STOP_FIXTURES = [("rmsc03", 123456789, 11 * 3600 * NS_S, "rmsc03_stop110000_1234
 
 
 def load_named(name):
-    """(fixture dict, trace, summary rows) of tests/golden/<name>.*"""
+    """(fixture dict, trace, summary rows) of tests/golden/<name>.*: <name>.json, <name>.npz and
+    <name>_summary.json, or the one packed <name>.npz of gen_fixtures.py --packed"""
+    if not os.path.exists(os.path.join(GOLDEN, name + ".json")):
+        z = np.load(os.path.join(GOLDEN, name + ".npz"))
+        return json.loads(str(z["final"])), z["trace"], json.loads(str(z["summary"]))
     with open(os.path.join(GOLDEN, name + ".json")) as f:
         d = json.load(f)
     with open(os.path.join(GOLDEN, name + "_summary.json")) as f:
