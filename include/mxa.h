@@ -292,8 +292,11 @@ int mxa_read_counters(mxa_handle* h, int64_t* out);
  * [4] value agents' resting orders taken with their ORDER_ACCEPTED inside such a wake
  * (value_order; at most [1]), [5] 0.  An in-place group leaves every observable of the queued
  * sequence in the env block, the counters above included; this count is the one thing that tells
- * the paths apart.  Reads, then clears.  Synchronous. */
-#define MXA_INPLACE_WORDS 6
+ * the paths apart.  Words [6..8] and [9..11]: draws the same runs took from the variate tables
+ * (include/mxa_variates.h) of the oracle stream and of the value agents' own streams, each as
+ * (hits, fills, serial fall-backs); all 0 in a configuration without tables.  Reads, then clears.
+ * Synchronous. */
+#define MXA_INPLACE_WORDS 12
 int mxa_read_inplace(mxa_handle* h, uint64_t* out);
 /* diagnostics: copy `bytes` raw bytes of env `env`'s HBM block starting at `offset`; and
  * the block's section offsets (Layout: ag, open, rng, lat, q, book, tx, trace) */
@@ -451,6 +454,7 @@ int mxa_read_book_log(mxa_handle* h, int32_t env, mxa_book_rec* out, int64_t cap
 #include "mxa_snap.h"
 #include "mxa_depth.h"
 #include "mxa_bars.h"
+#include "mxa_variates.h"
 
 /* parity probes: device numpy-legacy RNG (mode 0 u32, 1 double, 2 randint(a,b),
  * 3 normal(a,b), 4 exponential(a), 5 uniform(a,b)) and device glibc math (mode 0 log, 1 exp,

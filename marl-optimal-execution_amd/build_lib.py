@@ -41,7 +41,7 @@ CFG_FLAGS = {1: ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], 2: ["-fno-slp-vect
 
 
 def sources():
-    return [os.path.join(HERE, "csrc", d) for d in DEPS] + [os.path.join(ROOT, "include", h) for h in ("mxa.h", "mxa_snap.h", "mxa_depth.h", "mxa_bars.h")]
+    return [os.path.join(HERE, "csrc", d) for d in DEPS] + [os.path.join(ROOT, "include", h) for h in ("mxa.h", "mxa_snap.h", "mxa_depth.h", "mxa_bars.h", "mxa_variates.h")]
 
 
 def build_id(extra=()):

@@ -1356,6 +1356,30 @@ int mxa_rng_probe(int32_t device, uint32_t seed, int32_t mode, double a, double 
   return hipMemcpy(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost) == hipSuccess ? MXA_OK : MXA_EHIP;
 }
 
+// include/mxa_variates.h
+int mxa_variate_probe(int32_t device, uint32_t seed, const uint8_t* script, int32_t n, int32_t lookahead, double* out,
+                      uint64_t* state) {
+  if (n <= 0 || !script || !out || !state || lookahead < 2 || lookahead > 256) return MXA_EINVAL;
+  for (int32_t i = 0; i < n; i++)
+    if (script[i] > 3) return MXA_EINVAL;
+  if (hipSetDevice(device) != hipSuccess) return MXA_EHIP;
+  DevBuf<uint8_t> d_script;
+  DevBuf<double> d_out;
+  DevBuf<uint64_t> d_state, d_tab;
+  DevBuf<uint32_t> d_s;
+  if (d_script.alloc(n) != hipSuccess || d_out.alloc(2 * (size_t)n) != hipSuccess || d_state.alloc(6 * (size_t)n) != hipSuccess ||
+      d_tab.alloc(MXA_VT_BYTES / 8) != hipSuccess || d_s.alloc(2 * MXA_RNG_WORDS) != hipSuccess)
+    return MXA_ENOMEM;
+  if (hipMemcpy(d_script, script, (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(d_tab, 0, MXA_VT_BYTES) != hipSuccess)
+    return MXA_EHIP;
+  hipLaunchKernelGGL(mxa_variate_probe_kernel, dim3(1), dim3(64), 0, 0, seed, d_script.p, n, lookahead, d_out.p, d_state.p,
+                     d_s.p, d_tab.p);
+  if (hipGetLastError() != hipSuccess) return MXA_EHIP;
+  if (hipMemcpy(out, d_out, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return MXA_EHIP;
+  return hipMemcpy(state, d_state, sizeof(uint64_t) * 6 * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess ? MXA_OK : MXA_EHIP;
+}
+
 int mxa_math_probe(int32_t device, int32_t mode, const double* x, const double* y, double* out, int64_t n) {
   if (n <= 0 || !x || !out) return MXA_EINVAL;
   if (hipSetDevice(device) != hipSuccess) return MXA_EHIP;

@@ -31,6 +31,7 @@ struct Shape {
 constexpr int sq_lds(int cfg);
 constexpr int lat_lds(int cfg);
 constexpr Shape shape(int cfg);
+constexpr bool is_custom(int cfg);
 #ifndef MXA_RMSC03_WAVES
 #define MXA_RMSC03_WAVES 4
 #endif
@@ -249,11 +250,35 @@ constexpr int book_lds(int cfg) {
 #endif
 constexpr bool temper_fill(int cfg) { return (((MXA_TEMPER_FILL_MASK) >> cfg) & 1) != 0; }
 constexpr bool one_advance(int cfg) { return (((MXA_ONE_ADVANCE_MASK) >> cfg) & 1) != 0; }
+// The draw-ahead variate tables (DESIGN.md §3 "Variate tables", Appendix R.13; bit = config id, the
+// built-in configuration only: a runtime composition keeps its base's serial draws).  A unit outside
+// both masks compiles to the code it had before them.  MXA_VARIATE_TABLES 0: nowhere.
+// ... whose oracle stream O draws its normals from a table in LDS (MXA_VT_O_BYTES of the launch's block)
+#ifndef MXA_VARIATE_TABLES
+#define MXA_VARIATE_TABLES 1
+#endif
+#ifndef MXA_VARIATE_O_MASK
+#define MXA_VARIATE_O_MASK (1 << MXA_CFG_RMSC03)
+#endif
+// ... whose value agents draw their own streams' exponentials and normals from a table each in the
+// env block (Layout::off_vt, MXA_VT_BYTES per value agent)
+#ifndef MXA_VARIATE_AGENT_MASK
+#define MXA_VARIATE_AGENT_MASK (1 << MXA_CFG_RMSC03)
+#endif
+constexpr bool variate_o(int cfg) { return MXA_VARIATE_TABLES != 0 && (((MXA_VARIATE_O_MASK) >> cfg) & 1) != 0 && !is_custom(cfg); }
+constexpr bool variate_agent(int cfg) {
+  return MXA_VARIATE_TABLES != 0 && (((MXA_VARIATE_AGENT_MASK) >> cfg) & 1) != 0 && !is_custom(cfg);
+}
+// a table: 64 slots of (ret, cache) doubles and the descriptor's two words in LDS; 64 slots of
+// (e, ret, cache, 0) in the env block, the descriptor in the agent's record (AF_VT_*)
+#define MXA_VT_O_BYTES ((2 * 64 + 2) * 8)
+#define MXA_VT_BYTES 2048
 constexpr size_t lds_bytes(int cfg) {
   return (size_t)sq_lds(cfg) * 64 * (12 + (shape(cfg).pl ? 4 * shape(cfg).pw : 0)) + 512  // queue + EnvHdr
          + (size_t)shape(cfg).hot * 512                                                       // hot agent records
          + 1024                                                                               // RNG stream windows
-         + (size_t)lat_lds(cfg) * 8                                                           // exchange latency row
+         + (variate_o(cfg) ? MXA_VT_O_BYTES : 0)                                              // O's variate table
+         + (size_t)lat_lds(cfg) * 8                                                          // exchange latency row
          + (rp_hdr_lds(cfg) ? 256 : 0)                                                        // RpHdr (replay / gym)
          + (size_t)__builtin_popcount(book_lds(cfg)) * shape(cfg).so * 256                    // LDS book arrays
          + 256  // batched-push scratch: slot table
@@ -677,6 +702,8 @@ constexpr void layout(MxaParams& P, int cfg) {
   off = align_up(off + (P.md_sub ? (uint64_t)MD_MAX_SUBS * sizeof(SubRec) : 0), 256);
   L.off_md = off;
   off = align_up(off + (P.md_sub ? (uint64_t)P.n_agents * MD_WORDS * 4 : 0), 256);
+  L.off_vt = off;  // the value agents' variate tables (MXA_VARIATE_AGENT_MASK; no bytes elsewhere)
+  off = align_up(off + (variate_agent(cfg) ? (uint64_t)P.n_value * MXA_VT_BYTES : 0), 256);
   L.off_trace = (uint32_t)off;
   L.env_stride = off;  // without trace; the handle adds trace_cap records
 }

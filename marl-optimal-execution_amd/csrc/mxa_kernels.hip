@@ -467,6 +467,122 @@ template <bool B, int W, bool TF>
 DEV double rs_exponential(RSt<B, W, TF>& r, double scale) { return scale * -gm_log(1.0 - rs_double(r)); }
 template <bool B, int W, bool TF>
 DEV double rs_uniform(RSt<B, W, TF>& r, double lo, double hi) { return lo + (hi - lo) * rs_double(r); }
+// Variate tables (DESIGN.md §3 "Variate tables", Appendix R.13): a positional memo over a span of
+// up to 64 doubles of one stream, filled lane-parallel (lane = double index) and consulted by the
+// serial draw.  Double i of a table with base position b is the words b + 2i, b + 2i + 1; slot i
+// holds e = gm_log(1.0 - u_i) (EXP tables) and, for the polar attempt that starts at double i
+// (i + 1 < n), ret = f * x2 and cache = f * x1, whose accept bit is in the descriptor: the
+// operations of rs_double, rs_exponential and rs_gauss_serial in their order, so a hit returns the
+// bits the serial draw returns and leaves (p, hasg, gauss) as it does.  A table is a pure function
+// of the stream's words, so it may be dropped (n = 0) at any time; whatever reseeds a stream MUST
+// drop it (positions restart at 624).  The descriptor lives with its user (LDS beside the oracle
+// table, the value agent's record), so a lookup is one memory round trip: the slot's.
+// T: pointer to the slots' u64 words (LDS or global), VtIdx<EXP>::STRIDE words per slot.
+struct VtDesc {
+  u64 acc;  // bit i: the attempt that starts at double i is accepted (and i + 1 < n)
+  i32 b, n;  // base position, valid doubles
+};
+template <bool EXP>
+struct VtIdx {
+  static constexpr int STRIDE = EXP ? 4 : 2, RET = EXP ? 1 : 0, CACHE = RET + 1;
+};
+DEV u64 vt_uni(u64 v) {  // a word every lane loaded from one address, as a scalar
+  const u32 lo = (u32)__builtin_amdgcn_readfirstlane((i32)(u32)v), hi = (u32)__builtin_amdgcn_readfirstlane((i32)(u32)(v >> 32));
+  return ((u64)hi << 32) | lo;
+}
+// fill from position r.p: lane i is valid while both its words lie in the materialized double
+// buffer (rs_fill's test) and inside the first `cap` words; n ends at the first invalid lane
+template <bool EXP, class R, class T>
+DEV VtDesc vt_fill(const R& r, T tab, int cap = 128) {
+  typedef VtIdx<EXP> I;
+  const int lane = laneid();
+  const int q0 = r.p + 2 * lane, q1 = q0 + 1, b0 = q0 / MXA_MT_N, b1 = q1 / MXA_MT_N;
+  const bool ok = (cap >= 128 || 2 * lane + 1 < cap) && b0 >= r.m - 1 && b1 <= r.m;
+  u32 w0 = 0, w1 = 0;
+  if (ok) {
+    w0 = r.key[(b0 & 1) * MXA_MT_N + (q0 - b0 * MXA_MT_N)];
+    w1 = r.key[(b1 & 1) * MXA_MT_N + (q1 - b1 * MXA_MT_N)];
+  }
+  const i32 a = (i32)(mt_temper(w0) >> 5), b = (i32)(mt_temper(w1) >> 6);
+  const double u = ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
+  const u64 okb = bal(ok);
+  VtDesc d;
+  d.b = r.p;
+  d.n = ~okb == 0 ? 64 : ffs64(~okb);
+  if constexpr (EXP) {
+    tab[I::STRIDE * lane] = as_u(gm_log(1.0 - u));
+    tab[I::STRIDE * lane + 3] = 0;
+  }
+  const double x1 = 2.0 * u - 1.0;
+  const double x2 = __shfl_down(x1, 1, 64);
+  const double r2 = x1 * x1 + x2 * x2;
+  const bool acc = lane + 1 < d.n && !(r2 >= 1.0 || r2 == 0.0);
+  double f = 0.0;
+  if (acc) f = __builtin_sqrt(-2.0 * gm_log(r2) / r2);
+  tab[I::STRIDE * lane + I::RET] = as_u(acc ? f * x2 : 0.0);
+  tab[I::STRIDE * lane + I::CACHE] = as_u(acc ? f * x1 : 0.0);
+  d.acc = bal(acc);
+  wfence();
+  return d;
+}
+// the exponential's gm_log(1.0 - rs_double(r)); false: the table does not hold the double at r.p
+template <class R, class T>
+DEV bool vt_exp(R& r, T tab, const VtDesc& d, double& e) {
+  const u32 off = (u32)(r.p - d.b);
+  if ((off & 1u) || (off >> 1) >= (u32)d.n) return false;
+  e = as_d(vt_uni(tab[VtIdx<true>::STRIDE * (off >> 1)]));
+  r.p += 2;
+  return true;
+}
+// rs_gauss_serial without a cached value: the first accepted attempt among the doubles i, i + 2, ...
+// from r.p; false: misaligned, outside the span, or no accepted attempt inside it
+template <bool EXP, class R, class T>
+DEV bool vt_gauss(R& r, T tab, const VtDesc& d, double& g) {
+  typedef VtIdx<EXP> I;
+  const u32 off = (u32)(r.p - d.b), i = off >> 1;
+  if ((off & 1u) || i + 1 >= (u32)d.n) return false;
+  const u64 m = d.acc & (0x5555555555555555ull << (i & 1u)) & (~0ull << i);  // acc holds no attempt past n - 2
+  if (!m) return false;
+  const int j = ctz64(m);
+  g = as_d(vt_uni(tab[I::STRIDE * j + I::RET]));
+  r.gauss = as_d(vt_uni(tab[I::STRIDE * j + I::CACHE]));
+  r.hasg |= 1;
+  r.p = d.b + 2 * j + 4;
+  return true;
+}
+// the draws through a table: a miss refills from r.p (put(d) keeps the new descriptor) and retries
+// once, then runs the serial code.  count(what): 0 hit, 1 fill, 2 serial fall-back
+template <bool EXP, class R, class T, class P, class C>
+DEV double vt_draw_gauss(R& r, T tab, VtDesc d, P put, C count, int cap = 128) {
+  if (r.hasg & 1) return rs_gauss_serial(r);  // the cached value
+  double g;
+  if (MXA_RARE(!vt_gauss<EXP>(r, tab, d, g))) {
+    d = vt_fill<EXP>(r, tab, cap);
+    put(d);
+    count(1);
+    if (!vt_gauss<EXP>(r, tab, d, g)) {
+      count(2);
+      return rs_gauss_serial(r);
+    }
+  }
+  count(0);
+  return g;
+}
+template <class R, class T, class P, class C>
+DEV double vt_draw_exponential(R& r, T tab, VtDesc d, double scale, P put, C count, int cap = 128) {
+  double e;
+  if (MXA_RARE(!vt_exp(r, tab, d, e))) {
+    d = vt_fill<true>(r, tab, cap);
+    put(d);
+    count(1);
+    if (!vt_exp(r, tab, d, e)) {
+      count(2);
+      return rs_exponential(r, scale);
+    }
+  }
+  count(0);
+  return scale * -e;
+}
 // advance by k outputs without tempering them (build kernel only)
 template <int W, bool TF>
 DEV void rs_skip_words(RSt<true, W, TF>& r, i64 k) {
@@ -805,6 +921,11 @@ struct Eng {
   typedef typename std::conditional<TFILL, RSt<BUILD, (!BUILD || MXA_BUILD_WINDOWS != 0) ? RS_WIN : RS_HBM, true>,
                                     RSt<BUILD>>::type RS;
   typedef typename std::conditional<BUILD || !TFILL, RS, RSt<false, RS_HBM, true>>::type ARS;
+  // variate tables (mxa_config.h MXA_VARIATE_*_MASK): the oracle stream's in LDS, dropped at every
+  // launch start like the stream windows; one per value agent in the env block (Layout::off_vt),
+  // dropped by the build kernel.  The build kernel itself draws serially
+  static constexpr bool VT_O = !BUILD && mxa_cfg::variate_o(CFG);
+  static constexpr bool VT_A = !BUILD && mxa_cfg::variate_agent(CFG) && PC.n_value > 0;
   typedef typename std::conditional<PL_LDS, LDSP u32*, u32*>::type PlPtr;
   static constexpr int QCAP = SQ * 64;
   // event key t << KSH | recipient << 2 | type (13 recipient bits: random_fund_value's 5,101 agents)
@@ -1003,6 +1124,46 @@ struct Eng {
   LDSP RpHdr* rhl;
   LDSP i32* scr;     // [64] rank -> queue slot, then [64] u64 staged keys (MXA_QREG)
   LDSP u32* rwin;    // [4][64] output windows of the global RNG streams (RSt::lw)
+  // VT_O: the oracle stream's variate table below the windows: 64 slots, then its descriptor (accept
+  // bits; base | count << 32); derived where it is used, so the event loop carries no pointer for it
+  DEV LDSP u64* otab() { return (LDSP u64*)((LDSP char*)rwin - MXA_VT_O_BYTES); }
+  DEV VtDesc odesc() {
+    const u64 bn = vt_uni(otab()[129]);
+    return VtDesc{vt_uni(otab()[128]), (i32)(u32)bn, (i32)(u32)(bn >> 32)};
+  }
+  DEV void odesc_put(const VtDesc& d) {
+    if (lane == 0) {
+      otab()[128] = d.acc;
+      otab()[129] = (u64)(u32)d.b | ((u64)(u32)d.n << 32);
+    }
+    wfence();
+  }
+  // VT_A: the table of the value agent whose record is loaded; its descriptor is in the record
+  DEV u64* atab() { return (u64*)(env + PC.L.off_vt + (size_t)(cur_agent - PC.first_value) * MXA_VT_BYTES); }
+  DEV VtDesc adesc() { return VtDesc{(u64)rg64(AF_VT_ACC), rgi(AF_VT_B), rgi(AF_VT_N)}; }
+  DEV void adesc_put(const VtDesc& d) {
+    rs(AF_VT_B, (u32)d.b);
+    rs(AF_VT_N, (u32)d.n);
+    rs64(AF_VT_ACC, (i64)d.acc);
+  }
+  // what: 0 hit, 1 fill, 2 serial fall-back of user u (0 the oracle stream, 1 the value agents'),
+  // counted by the instrumented kernels next to the in-place groups (mxa_read_inplace words 6-11)
+  template <int USER>
+  DEV void vt_count(int what) {
+    if constexpr (INSTR && !BUILD) {
+      if ((hash_on || trace) && lane == 0) atomicAdd(&g_mxa_inplace[6 + 3 * USER + what], 1ull);
+    }
+  }
+  // the normal draws of the two users (loc + scale * legacy_gauss, as rs_normal)
+  DEV double o_normal(RS& O, double loc, double scale) {
+    if constexpr (VT_O) return loc + scale * vt_draw_gauss<false>(O, otab(), odesc(), [&](const VtDesc& d) { odesc_put(d); }, [&](int w) { vt_count<0>(w); });
+    else return rs_normal(O, loc, scale);
+  }
+  template <bool VAL>
+  DEV double agent_normal(ARS& A, double loc, double scale) {
+    if constexpr (VAL && VT_A) return loc + scale * vt_draw_gauss<true>(A, atab(), adesc(), [&](const VtDesc& d) { adesc_put(d); }, [&](int w) { vt_count<1>(w); });
+    else return rs_normal(A, loc, scale);
+  }
 
   static constexpr size_t LDS_Q = (size_t)QCL * (12 + (PL_LDS ? 4 * PW : 0));
   DEV Eng(char* e, char* lds, i32 tcap, const RpCtx* ctx = nullptr, BlRec* bl = nullptr, i32 bl_cap = 0)
@@ -1847,7 +2008,7 @@ struct Eng {
     double scale = (h.o_th2 / (2 * gamma)) * (1 - rdl_d(ex, 1));
     (void)theta;
     RS O = grs(1);
-    double v = rs_normal(O, loc, scale);
+    double v = o_normal(O, loc, scale);
     grs_put(1, O);
     v += v_adj;
     if (!(v > 0)) v = 0;
@@ -1869,19 +2030,21 @@ struct Eng {
       h.o_mst = pt + (i64)rs_exponential(G, 1.0 / PC.o_lambda);
       grs_put(0, G);
       RS O = grs(1);
-      double msv = rs_normal(O, PC.o_msmean, __builtin_sqrt(PC.o_msvar));
+      double msv = o_normal(O, PC.o_msmean, __builtin_sqrt(PC.o_msvar));
       h.o_msv = rs_randint(O, 0, 2) == 0 ? msv : -msv;
       grs_put(1, O);
     }
     return o_compute(t, 0, pt, pv);
   }
+  // VAL: the observation is a value agent's (its draw may come from the agent's variate table)
+  template <bool VAL = false>
   DEV i64 o_observe(i64 t, double sigma_n) {
     PROF_SCOPE(69);
     if constexpr (EXT) {  // ExternalFileOracle.observePrice (ExternalFileOracle.py:110-129): no clamp, no draws
       const double tp = efo_price(t);
       if (sigma_n == 0) return py_round(tp);
       ARS A = agent_rs();
-      const i64 obs = py_round(rs_normal(A, tp, __builtin_sqrt(sigma_n)));
+      const i64 obs = py_round(agent_normal<VAL>(A, tp, __builtin_sqrt(sigma_n)));
       agent_rs_put(A);
       return obs;
     }
@@ -1890,7 +2053,7 @@ struct Eng {
     else r_t = t >= PC.mkt_close ? o_advance(PC.mkt_close - 1) : o_advance(t);
     if (sigma_n == 0) return (i64)r_t;
     ARS A = agent_rs();
-    i64 obs = py_round(rs_normal(A, r_t, __builtin_sqrt(sigma_n)));
+    i64 obs = py_round(agent_normal<VAL>(A, r_t, __builtin_sqrt(sigma_n)));
     agent_rs_put(A);
     return obs;
   }
@@ -2973,7 +3136,9 @@ struct Eng {
     fl_set(FL_TRADING, true);
     if (fl(FL_MKT_CLOSED) && fl(FL_DAILY_CLOSE)) return false;
     ARS A = agent_rs();
-    double dt = rs_exponential(A, 1.0 / PC.v_lambda);
+    double dt;
+    if constexpr (VT_A) dt = vt_draw_exponential(A, atab(), adesc(), 1.0 / PC.v_lambda, [&](const VtDesc& d) { adesc_put(d); }, [&](int w) { vt_count<1>(w); });
+    else dt = rs_exponential(A, 1.0 / PC.v_lambda);
     agent_rs_put(A);
     wakeup_at(cur_agent, cur + py_round(dt));
     if (fl(FL_MKT_CLOSED) && !fl(FL_DAILY_CLOSE)) {
@@ -2988,7 +3153,7 @@ struct Eng {
   // after the group's own); returns the pops taken beyond the reply's
   template <bool INPL = false>
   DEV int value_place(i64 room = 0) {
-    i64 obs = o_observe(cur, v_sigma_n());
+    i64 obs = o_observe<true>(cur, v_sigma_n());
     i64 r_T = bayes_r_T(obs, PC.v_kappa, v_rbar(), v_sigma_n(), PC.v_sigma_s);
     i32 bid, ask;
     bool hb = known_bid(bid), ha = known_ask(ask);
@@ -4800,6 +4965,8 @@ struct Eng {
     qcount = h.q_count;
     maxq = h.max_q;
     if (lane < 4) h.rs_wn[lane] = 0;  // the LDS stream windows did not survive the last launch
+    if constexpr (VT_O)
+      if (lane == 0) otab()[129] = 0;  // nor did the oracle stream's variate table
     wfence();
     if constexpr (KREG) {
       kp = h.rs_pos[KS];
@@ -6165,6 +6332,11 @@ struct Builder : Eng<CFG, true> {
       for (int i = this->lane; i < (int)(sizeof(EnvHdr) / 4); i += 64) hw[i] = 0;
       wfence();
     }
+    // every stream is reseeded below: the value agents' variate tables name positions of the old ones
+    if constexpr (mxa_cfg::variate_agent(CFG) && E::PC.n_value > 0) {
+      u64* vt = (u64*)(this->env + P.L.off_vt);
+      for (int i = this->lane; i < P.n_value * (MXA_VT_BYTES / 8); i += 64) vt[i] = 0;
+    }
     this->hash = FNV_OFF;
     this->status = ST_RUNNING;
     this->err = 0;
@@ -6724,6 +6896,44 @@ __global__ __launch_bounds__(64) void mxa_rng_probe_kernel(uint32_t seed, int mo
     default: v = mxa::rs_uniform(r, a, b); break;
     }
     if (__lane_id() == 0) out[i] = v;
+  }
+}
+// a script of draws on one stream, once through a variate table (pass 0) and once through the serial
+// code alone (pass 1): the device functions the engine's value agents draw with (vt_draw_*, an EXP
+// table in global memory).  kind 0 exponential(1), 1 standard normal, 2 one word, 3 randint(0, 100).
+// out [2][n]; state [2][n][3] = (p, hasg, gauss bits) after every draw.  scratch: two streams' MT
+// double buffers; tab: MXA_VT_BYTES, zeroed.  `cap`: the words of look-ahead a fill may span
+__global__ __launch_bounds__(64) void mxa_variate_probe_kernel(uint32_t seed, const uint8_t* script, int n, int cap, double* out,
+                                                               uint64_t* state, uint32_t* scratch, uint64_t* tab) {
+  for (int pass = 0; pass < 2; pass++) {
+    mxa::RSt<true> r;
+    r.lw = nullptr;  // draws read the MT block in HBM
+    r.lw0 = r.lwn = 0;
+    r.key = scratch + pass * MXA_RNG_WORDS;
+    mxa::mt_seed(r.key, seed);
+    r.p = MXA_MT_N;
+    r.m = 0;
+    r.hasg = 0;
+    r.gauss = 0;
+    auto none = [](int) {};
+    mxa::VtDesc d{0, 0, 0};
+    auto put = [&](const mxa::VtDesc& x) { d = x; };
+    for (int i = 0; i < n; i++) {
+      const int kind = script[i];
+      double v;
+      if (pass == 0) mxa::rs_maint(r, MXA_AGENT_LA);  // the engine's look-ahead at an event boundary
+      if (kind == 0) v = pass == 0 ? mxa::vt_draw_exponential(r, tab, d, 1.0, put, none, cap) : mxa::rs_exponential(r, 1.0);
+      else if (kind == 1) v = pass == 0 ? mxa::vt_draw_gauss<true>(r, tab, d, put, none, cap) : mxa::rs_gauss_serial(r);
+      else if (kind == 2) v = (double)mxa::rs_u32(r);
+      else v = (double)mxa::rs_randint(r, 0, 100);
+      if (__lane_id() == 0) {
+        const size_t k = (size_t)pass * n + i;
+        out[k] = v;
+        state[3 * k] = (uint64_t)(uint32_t)r.p;
+        state[3 * k + 1] = (uint64_t)(uint32_t)r.hasg;
+        state[3 * k + 2] = mxa::as_u(r.gauss);
+      }
+    }
   }
 }
 __global__ void mxa_math_probe_kernel(int mode, const double* x, const double* y, double* out, int64_t n) {

@@ -308,6 +308,7 @@ typedef struct {
   int32_t oh_cap, hbl_range;    // order-history ring records; HBL price-histogram bins (0: none)
   uint64_t off_oh, off_hh;      // order-history ring; HBL histogram scratch (u64 bins)
   uint64_t off_sub, off_md;     // subscription table [MD_MAX_SUBS]; per-agent MARKET_DATA slots
+  uint64_t off_vt;              // variate tables of the value agents' streams [n_value][MXA_VT_BYTES] (mxa_config.h)
 } Layout;
 
 // agent record: 128 dwords (512 B); lane i of the owning wave holds dwords 2i, 2i+1
@@ -331,6 +332,9 @@ enum {
   // MarketReplayAgent: the next wakeup group (the reference's wakeup index) and the tape records
   // handled, in its LDS-resident record (RpHdr::mr_done stays the copy other agents read)
   AF_MR_WI = 46, AF_MR_DONE = 47,
+  // ValueAgent: the descriptor of its stream's variate table (Layout::off_vt): base position, valid
+  // doubles, accept bits (int64); zero in a fresh record: an empty table
+  AF_VT_B = 46, AF_VT_N = 47, AF_VT_ACC = 48,
   AF_MIDS = 66,       // 50 x int32 (2*mid ring), momentum
   AF_STREAM_N = 66,   // HBL: epochs of the last QUERY_ORDER_STREAM reply (momentum's AF_MIDS area)
   AF_STREAM_HI = 68,  // HBL: absolute history epoch of its first entry (history[1]), int64

@@ -171,8 +171,12 @@ BARS_BINDINGS = {
     "mxa_read_bars": ([_P, _I64, _I64, _I32, _P, _P], _I32),
     "mxa_bars_from_records": ([_P, _I32, _P, _I64, _P, _I32, _I64, _I64, _I32, _P, _P], _I32),
 }
+# the export of include/mxa_variates.h (the variate tables' probe; a part of mxa.h's C-ABI too)
+VARIATE_BINDINGS = {
+    "mxa_variate_probe": ([_I32, _U32, _P, _I32, _I32, _P, _P], _I32),
+}
 COUNTER_WORDS = 34  # include/mxa.h MXA_COUNTER_WORDS
-INPLACE_WORDS = 6  # include/mxa.h MXA_INPLACE_WORDS
+INPLACE_WORDS = 12  # include/mxa.h MXA_INPLACE_WORDS
 RECORD_WORDS = 12  # include/mxa.h MXA_RECORD_WORDS
 
 _lib = None
@@ -190,7 +194,7 @@ def load():
         raise MxaError("libmxa.so not built (%s); run __graft_entry__.build()" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in list(BINDINGS.items()) + list(SNAPSHOT_BINDINGS.items()) + list(DEPTH_BINDINGS.items()) \
-            + list(BARS_BINDINGS.items()):
+            + list(BARS_BINDINGS.items()) + list(VARIATE_BINDINGS.items()):
         if hasattr(L, name):  # (MXA_LIB may name a variant build that lacks some)
             f = getattr(L, name)
             f.argtypes, f.restype = argtypes, restype

@@ -68,7 +68,9 @@ class Handle:
         resting orders with their acknowledgement (inside such a wake), 0] taken in place by
         the instrumented runs (parity hash on) of this configuration's handles since the last call
         (include/mxa.h mxa_read_inplace: read, then cleared).  The env blocks cannot tell: an in-place
-        group leaves every observable of the queued sequence"""
+        group leaves every observable of the queued sequence.  Words 6-8 and 9-11: the draws those
+        runs took from the variate tables of the oracle stream and of the value agents' streams, as
+        (hits, fills, serial fall-backs)"""
         out = np.zeros(_lib.INPLACE_WORDS, dtype=np.uint64)
         self._check(self.L.mxa_read_inplace(self._h, out.ctypes.data), "mxa_read_inplace")
         return out
