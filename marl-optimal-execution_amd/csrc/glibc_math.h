@@ -23,13 +23,9 @@
 // private copy of each next to the device code and reaches it pc-relatively, one scalar load per
 // read.  As `static __device__ __constant__` variables HIP made them externally visible (the host
 // can name a __constant__), and position-independent code then read every table address from the
-// GOT first: two dependent scalar-memory round trips where one is needed.  -DGM_TABLES_GOT restores
-// that form (the A/B variant of DESIGN.md Appendix R.10).
-#ifdef GM_TABLES_GOT
-#define GM_TABLE_QUAL static __device__ __constant__ const
-#else
+// GOT first: two dependent scalar-memory round trips where one is needed (measured in DESIGN.md
+// Appendix R.10).
 #define GM_TABLE_QUAL static constexpr
-#endif
 #else
 #define GM_FN static inline
 #define GM_BIG static inline

@@ -100,49 +100,18 @@ constexpr bool is_custom(int cfg);
 // obi_rmsc02 307 vs 305 ms, rmsc03 39.4 vs 38.2 ms (ab_dwb_levels.txt), off
 #define MXA_DIRTY_WB_MASK ((1 << 9) | (1 << 10) | (1 << 11) | (1 << 12) | (1 << MXA_CFG_RMSC01) | (1 << MXA_CFG_RMSC02))
 #endif
-// configurations whose POV market maker's once-a-wake exchange queries (QUERY_SPREAD,
-// QUERY_TRANSACTED_VOLUME) and their replies are handled inside the wakeup's own pop when they
-// are the forced next four pops (Eng::mm_cycle, DESIGN.md §3 "Queries answered in place"; bit =
-// config id).  Only the zero-delay, zero-latency configurations qualify at compile time
-// (Eng::SYNCQ); the others compile to the queued path whatever their bit says
-#ifndef MXA_SYNC_QUERY_MASK
-#define MXA_SYNC_QUERY_MASK ((1 << MXA_CFG_RMSC03) | (1 << MXA_CFG_RMSC03_RL))
-#endif
-// ... and whose value agents' wakeups take their CANCEL_ORDER / QUERY_SPREAD round trip the same way
-// (Eng::value_cycle)
-#ifndef MXA_SYNC_VALUE_MASK
-#define MXA_SYNC_VALUE_MASK MXA_SYNC_QUERY_MASK
-#endif
-// ... and whose value agents' resting LIMIT_ORDER and its ORDER_ACCEPTED ride in that pop as well
-// (Eng::value_order; needs the value bit too)
-#ifndef MXA_SYNC_ORDER_MASK
-#define MXA_SYNC_ORDER_MASK MXA_SYNC_QUERY_MASK
-#endif
-// 1: the order enters the book in place but its ORDER_ACCEPTED is still pushed and popped (the A/B
-// variant of Appendix R.11)
-#ifndef MXA_ORDER_ACK_QUEUED
-#define MXA_ORDER_ACK_QUEUED 0
-#endif
-// ... and whose market maker's cancel and ladder runs, with the exchange's replies to them, ride in
-// the same pop when the volume reply re-quotes (Eng::mm_ladder_cycle; needs the query bit too)
-#ifndef MXA_SYNC_LADDER_MASK
-#define MXA_SYNC_LADDER_MASK MXA_SYNC_QUERY_MASK
-#endif
-// 1: only the exchange's side of that group in place, ORDER_CANCELLED / ORDER_ACCEPTED still pushed and
-// popped as runs (the A/B variant of DESIGN.md Appendix R.8)
-#ifndef MXA_LADDER_REPLIES_QUEUED
-#define MXA_LADDER_REPLIES_QUEUED 0
-#endif
-// ... and whose in-place groups ask only that no pending event sorts before the group's last pop
-// (key below (t, agent + 1)), not that none has time <= t: the market maker takes its group at the
-// instants it shares with the momentum agents (Eng::none_before, DESIGN.md §3 "The bound")
-#ifndef MXA_SYNC_BOUND_MASK
-#define MXA_SYNC_BOUND_MASK MXA_SYNC_QUERY_MASK
-#endif
-// 1: Eng::value_cycle loads the agent's open-order chunk before the wakeup's head instead of after
-// it
-#ifndef MXA_VALUE_OPEN_EARLY
-#define MXA_VALUE_OPEN_EARLY 0
+// configurations whose forced exchange round trips are handled inside the wakeup's own pop
+// (DESIGN.md §3 "Queries answered in place"; bit = config id): the POV market maker's once-a-wake
+// QUERY_SPREAD / QUERY_TRANSACTED_VOLUME and their replies (Eng::mm_cycle), its cancel and ladder
+// runs with the exchange's replies to them when the volume reply re-quotes (Eng::mm_ladder_cycle),
+// the value agents' CANCEL_ORDER / QUERY_SPREAD round trip (Eng::value_cycle) and their resting
+// LIMIT_ORDER with its ORDER_ACCEPTED (Eng::value_order, Appendix R.11).  A group asks only that no
+// pending event sorts before its last pop (key below (t, agent + 1)), so the market maker takes
+// its group at the instants it shares with the momentum agents (Eng::none_before, §3 "The bound").
+// Only the zero-delay, zero-latency configurations qualify at compile time (Eng::INPLACE); the
+// others compile to the queued path whatever their bit says
+#ifndef MXA_INPLACE_MASK
+#define MXA_INPLACE_MASK ((1 << MXA_CFG_RMSC03) | (1 << MXA_CFG_RMSC03_RL))
 #endif
 #ifndef MXA_OPEN_RFD
 #define MXA_OPEN_RFD 128
@@ -232,16 +201,16 @@ constexpr int book_lds(int cfg) {
 }
 // The RNG stream windows (DESIGN.md §3 "RNG stream windows", Appendix R.12; bit = config id).  A unit
 // outside the first mask compiles to the code it had before it.
-// ... whose windows hold tempered outputs, so a draw is the LDS read alone (MXA_TEMPER_AT_FILL 0:
-// nowhere).  A bit is set where the configuration was measured with it and passed: rmsc03 x4096
-// 20.81 -> 20.34 ms; with the next mask's bit sparse_zi_100 104.2 -> 101.0, value_noise 17.1 -> 16.0.
-// rmsc01 neutral, off; rmsc03_rl loses with it (21.76 -> 22.31), off
+// ... whose windows hold tempered outputs, so a draw is the LDS read alone.  A bit is set where
+// the configuration was measured with it and passed: rmsc03 x4096 20.81 -> 20.34 ms; with the
+// next mask's bit sparse_zi_100 104.2 -> 101.0, value_noise 17.1 -> 16.0.  rmsc01 neutral, off;
+// rmsc03_rl loses with it (21.76 -> 22.31), off
 #ifndef MXA_TEMPER_FILL_MASK
 #define MXA_TEMPER_FILL_MASK ((1 << MXA_CFG_RMSC03) | (1 << MXA_CFG_SPARSE_ZI_100) | (1 << MXA_CFG_VALUE_NOISE))
 #endif
-// ... whose o_observe calls o_advance once (MXA_ONE_ADVANCE 0: nowhere).  This part did NOT pass the
-// A/B rule on its own (rmsc03: every run below every run of the parent, but 0.12 ms under its fastest
-// against a spread of 0.19) and is neutral in time on top of the tempered fill.  It is on wherever
+// ... whose o_observe calls o_advance once.  This part did NOT pass the A/B rule on its own
+// (rmsc03: every run below every run of the parent, but 0.12 ms under its fastest against a
+// spread of 0.19) and is neutral in time on top of the tempered fill.  It is on wherever
 // the fill is, against "a part that does not pass stays off", for what it does to the code: the fill
 // alone grows the rmsc03 run kernel's VGPR spills 226 -> 248, with this they are 219, SGPR spills
 // 56 -> 42, 31.6 k -> 27.2 k static instructions, 166 -> 142 kB
@@ -252,11 +221,8 @@ constexpr bool temper_fill(int cfg) { return (((MXA_TEMPER_FILL_MASK) >> cfg) & 
 constexpr bool one_advance(int cfg) { return (((MXA_ONE_ADVANCE_MASK) >> cfg) & 1) != 0; }
 // The draw-ahead variate tables (DESIGN.md §3 "Variate tables", Appendix R.13; bit = config id, the
 // built-in configuration only: a runtime composition keeps its base's serial draws).  A unit outside
-// both masks compiles to the code it had before them.  MXA_VARIATE_TABLES 0: nowhere.
+// both masks compiles to the code it had before them.
 // ... whose oracle stream O draws its normals from a table in LDS (MXA_VT_O_BYTES of the launch's block)
-#ifndef MXA_VARIATE_TABLES
-#define MXA_VARIATE_TABLES 1
-#endif
 #ifndef MXA_VARIATE_O_MASK
 #define MXA_VARIATE_O_MASK (1 << MXA_CFG_RMSC03)
 #endif
@@ -265,10 +231,8 @@ constexpr bool one_advance(int cfg) { return (((MXA_ONE_ADVANCE_MASK) >> cfg) & 
 #ifndef MXA_VARIATE_AGENT_MASK
 #define MXA_VARIATE_AGENT_MASK (1 << MXA_CFG_RMSC03)
 #endif
-constexpr bool variate_o(int cfg) { return MXA_VARIATE_TABLES != 0 && (((MXA_VARIATE_O_MASK) >> cfg) & 1) != 0 && !is_custom(cfg); }
-constexpr bool variate_agent(int cfg) {
-  return MXA_VARIATE_TABLES != 0 && (((MXA_VARIATE_AGENT_MASK) >> cfg) & 1) != 0 && !is_custom(cfg);
-}
+constexpr bool variate_o(int cfg) { return (((MXA_VARIATE_O_MASK) >> cfg) & 1) != 0 && !is_custom(cfg); }
+constexpr bool variate_agent(int cfg) { return (((MXA_VARIATE_AGENT_MASK) >> cfg) & 1) != 0 && !is_custom(cfg); }
 // a table: 64 slots of (ret, cache) doubles and the descriptor's two words in LDS; 64 slots of
 // (e, ret, cache, 0) in the env block, the descriptor in the agent's record (AF_VT_*)
 #define MXA_VT_O_BYTES ((2 * 64 + 2) * 8)

@@ -87,8 +87,7 @@ MxaEntry make_entry() {
     // 1190 vs 1245; rmsc01 and sparse_zi_1000 measured the other way in round 2 (1201 vs 1147,
     // 986 vs 976), but with the event-class counters in the instrumented kernel (round 3, s10)
     // the plain one wins there too: rmsc01 1047 vs 1082 ms, sparse_zi_1000 916 vs 920
-    constexpr bool fast = true;
-    if constexpr (fast) e.run_fast = launch_run<CFG, false, false>;
+    e.run_fast = launch_run<CFG, false, false>;
     e.stop_log = launch_stop<CFG, true>;
   }
 #ifndef MXA_NO_GYM

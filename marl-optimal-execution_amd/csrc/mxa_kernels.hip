@@ -34,13 +34,10 @@
 // in many draws) state them for the configurations of MXA_HINT_MASK (bit = config id: the unit's
 // -DMXA_INST_CFG, or a single-configuration variant build's); every other unit compiles the plain
 // condition.  Only wave-uniform branches carry one: a divergent branch is structurized and ignores
-// it.  MXA_HINT_GROUPS (bit 0 errors and fall-backs, bit 1 RNG and math) builds the A/B variants of
-// DESIGN.md Appendix R.10; weights on the loop's own dispatch order were measured there and lost.
+// it.  Both kinds are measured in DESIGN.md Appendix R.10; weights on the loop's own dispatch order
+// were measured there and lost.
 #ifndef MXA_HINT_MASK
 #define MXA_HINT_MASK ((1 << 0) | (1 << 4))  // MXA_CFG_RMSC03, MXA_CFG_RMSC03_RL
-#endif
-#ifndef MXA_HINT_GROUPS
-#define MXA_HINT_GROUPS 3
 #endif
 #if defined(MXA_INST_CFG)
 #define MXA_HINT_ON (((MXA_HINT_MASK) >> (MXA_INST_CFG)) & 1)
@@ -53,18 +50,15 @@
 #endif
 #define MXA_EXPECT_(x, v) __builtin_expect(!!(x), v)  // (!!: many conditions are 64-bit ballots)
 #define MXA_PROB_(x, v, p) __builtin_expect_with_probability(!!(x), v, p)
-#if MXA_HINT_ON && ((MXA_HINT_GROUPS) & 1)
+#if MXA_HINT_ON
 #define MXA_LIKELY(x) MXA_EXPECT_(x, 1)
 #define MXA_UNLIKELY(x) MXA_EXPECT_(x, 0)
-#else
-#define MXA_LIKELY(x) (x)
-#define MXA_UNLIKELY(x) (x)
-#endif
-#if MXA_HINT_ON && ((MXA_HINT_GROUPS) & 2)
 #define MXA_RARE(x) MXA_EXPECT_(x, 0)
 #define MXA_RARE_P(x, p) MXA_PROB_(x, 1, p)  // true with probability p
 #define GM_UNLIKELY(x) MXA_EXPECT_(x, 0)
 #else
+#define MXA_LIKELY(x) (x)
+#define MXA_UNLIKELY(x) (x)
 #define MXA_RARE(x) (x)
 #define MXA_RARE_P(x, p) (x)
 #endif
@@ -312,17 +306,9 @@ DEV void mt_gen_pair(u32* k1, int b1, u32* k2, int b2, bool two) {
   }
   wfence();
 }
-DEV void mt_gen_block_batched(u32* key, int b) { mt_gen_pair(key, b, key, b, false); }
-
 // the build kernel's block generation (the run kernel keeps mt_gen_block: a register-staged
 // form inlined into the event loop cost every configuration 1-3 %)
-#ifndef MXA_BUILD_BATCHED_GEN
-#define MXA_BUILD_BATCHED_GEN 1
-#endif
-DEV void mt_gen_build(u32* key, int b) {
-  if constexpr (MXA_BUILD_BATCHED_GEN) mt_gen_block_batched(key, b);
-  else mt_gen_block(key, b);
-}
+DEV void mt_gen_build(u32* key, int b) { mt_gen_pair(key, b, key, b, false); }
 
 // init_genrand (numpy _legacy_seeding with an int) into block 0: every lane runs the
 // recurrence, lane (i % 64) stores word i.
@@ -335,25 +321,6 @@ DEV void mt_seed(u32* key, u32 s) {
   wfence();
 }
 
-// the build kernel's draws through LDS windows too (one coalesced 64-word fill instead of a
-// dependent load per word): G/O/K/L their run-kernel windows, an agent stream the L window (the
-// build never draws from L)
-#ifndef MXA_BUILD_WINDOWS
-#define MXA_BUILD_WINDOWS 1
-#endif
-// 1: the configurations of MXA_TEMPER_FILL_MASK keep tempered outputs in their windows (the four
-// xor-shift steps run once per fill, 64 lanes wide on the VALU) and a draw is the LDS read alone;
-// elsewhere, and with 0 everywhere, a window holds the state words and every draw tempers its
-// word on the scalar unit
-#ifndef MXA_TEMPER_AT_FILL
-#define MXA_TEMPER_AT_FILL 1
-#endif
-// 1: in the configurations of MXA_ONE_ADVANCE_MASK o_observe clamps the time and calls o_advance
-// once; elsewhere, and with 0 everywhere, one call per side of the clamp, which inlines the
-// oracle's advance twice into every value_place (Appendix R.12)
-#ifndef MXA_ONE_ADVANCE
-#define MXA_ONE_ADVANCE 1
-#endif
 DEV u32 mt_temper(u32 y) {
   y ^= (y >> 11);
   y ^= (y << 7) & 0x9d2c5680u;
@@ -381,7 +348,7 @@ DEV void rs_fill(RSt<B, W, TF>& r) {
 }
 template <bool B, int W, bool TF>
 DEV u32 rs_u32(RSt<B, W, TF>& r) {
-  if constexpr (W == RS_WIN || (W == RS_PTR && (!B || MXA_BUILD_WINDOWS))) {
+  if constexpr (W == RS_WIN || W == RS_PTR) {
     if (W == RS_WIN || r.lw) {
       u32 off = (u32)(r.p - r.lw0);
       if (MXA_RARE(off >= (u32)r.lwn)) {  // the window refill: one word in 64
@@ -440,10 +407,6 @@ DEV i64 rs_randint(RSt<B, W, TF>& r, i64 lo, i64 hi) {
 // 54.4 k instructions); removed in round 5
 template <bool B, int W, bool TF>
 DEV double rs_gauss(RSt<B, W, TF>& r) {
-  return rs_gauss_serial(r);
-}
-template <bool B, int W, bool TF>
-DEV double rs_gauss_serial(RSt<B, W, TF>& r) {
   if (r.hasg & 1) {
     double t = r.gauss;
     r.hasg &= ~1;
@@ -472,7 +435,7 @@ DEV double rs_uniform(RSt<B, W, TF>& r, double lo, double hi) { return lo + (hi 
 // serial draw.  Double i of a table with base position b is the words b + 2i, b + 2i + 1; slot i
 // holds e = gm_log(1.0 - u_i) (EXP tables) and, for the polar attempt that starts at double i
 // (i + 1 < n), ret = f * x2 and cache = f * x1, whose accept bit is in the descriptor: the
-// operations of rs_double, rs_exponential and rs_gauss_serial in their order, so a hit returns the
+// operations of rs_double, rs_exponential and rs_gauss in their order, so a hit returns the
 // bits the serial draw returns and leaves (p, hasg, gauss) as it does.  A table is a pure function
 // of the stream's words, so it may be dropped (n = 0) at any time; whatever reseeds a stream MUST
 // drop it (positions restart at 624).  The descriptor lives with its user (LDS beside the oracle
@@ -534,7 +497,7 @@ DEV bool vt_exp(R& r, T tab, const VtDesc& d, double& e) {
   r.p += 2;
   return true;
 }
-// rs_gauss_serial without a cached value: the first accepted attempt among the doubles i, i + 2, ...
+// rs_gauss without a cached value: the first accepted attempt among the doubles i, i + 2, ...
 // from r.p; false: misaligned, outside the span, or no accepted attempt inside it
 template <bool EXP, class R, class T>
 DEV bool vt_gauss(R& r, T tab, const VtDesc& d, double& g) {
@@ -554,7 +517,7 @@ DEV bool vt_gauss(R& r, T tab, const VtDesc& d, double& g) {
 // once, then runs the serial code.  count(what): 0 hit, 1 fill, 2 serial fall-back
 template <bool EXP, class R, class T, class P, class C>
 DEV double vt_draw_gauss(R& r, T tab, VtDesc d, P put, C count, int cap = 128) {
-  if (r.hasg & 1) return rs_gauss_serial(r);  // the cached value
+  if (r.hasg & 1) return rs_gauss(r);  // the cached value
   double g;
   if (MXA_RARE(!vt_gauss<EXP>(r, tab, d, g))) {
     d = vt_fill<EXP>(r, tab, cap);
@@ -562,7 +525,7 @@ DEV double vt_draw_gauss(R& r, T tab, VtDesc d, P put, C count, int cap = 128) {
     count(1);
     if (!vt_gauss<EXP>(r, tab, d, g)) {
       count(2);
-      return rs_gauss_serial(r);
+      return rs_gauss(r);
     }
   }
   count(0);
@@ -598,18 +561,6 @@ DEV void rs_skip_words(RSt<true, W, TF>& r, i64 k) {
 // an agent event draws a few dozen words at most (the MarketMakerAgent's ladder sizes), and most
 // agents of the wide configurations draw a few words per session, so their second block is never
 // built.  A draw past the look-ahead is still ERR_RNG_OVERRUN, never a silent value.
-#ifndef MXA_MAINT_LANES
-#define MXA_MAINT_LANES 1
-#endif
-#ifndef MXA_WAKE_LANES
-#define MXA_WAKE_LANES 1
-#endif
-#ifndef MXA_ZI_THETA_LANES
-#define MXA_ZI_THETA_LANES 1
-#endif
-#ifndef MXA_SEED_TILE
-#define MXA_SEED_TILE 1
-#endif
 #ifndef MXA_AGENT_LA
 #define MXA_AGENT_LA 256
 #endif
@@ -837,18 +788,18 @@ struct ProfScope {
 #endif
 // diagnostics build (-DMXA_RP_CHECK): the replay book's computed indices are range-checked before
 // the global access they address; a bad one prints and ends the env with ERR_BAD_CONFIG
-// instead of faulting the device
+// instead of faulting the device (a fourth argument: what a non-void function then returns)
 #ifdef MXA_RP_CHECK
-#define RPCHK(c, what, v)                                                                     \
+#define RPCHK(c, what, v, ...)                                                                \
   do {                                                                                        \
     if (!(c)) {                                                                               \
       if (lane == 0) printf("RPCHK %s = %lld at pop %lld\n", what, (long long)(v), (long long)pops); \
       fail(ERR_BAD_CONFIG);                                                                   \
-      return;                                                                                 \
+      return __VA_ARGS__;                                                                     \
     }                                                                                         \
   } while (0)
 #else
-#define RPCHK(c, what, v)
+#define RPCHK(c, what, v, ...)
 #endif
 template <int CFG, bool BUILD = false, bool LOG = false, bool INSTR = true>
 struct Eng {
@@ -911,15 +862,21 @@ struct Eng {
   // the CANCELLED shortcut (open-order list) stays off
   static constexpr bool RP_FAST = !BUILD && RP && PC.default_comp_delay == 0 && PC.ex_comp == 0;
   static constexpr int ACK_LIMIT = GYM ? PC.first_rl : PC.n_agents;  // background agents 1..ACK_LIMIT-1
-  // RNG stream handles.  A unit with the tempered fill knows at compile time how each stream
-  // reads: G/O/K/L (RS) through their windows (the build kernel's follow MXA_BUILD_WINDOWS), an
-  // agent's own stream (ARS, Agent.random_state) from HBM; the build kernel's agent draws go
-  // through the L window.  Every other unit keeps the one handle type whose draws test the window
-  // pointer (RS_PTR): its code is the code it was measured with
-  static constexpr bool TFILL = MXA_TEMPER_AT_FILL != 0 && mxa_cfg::temper_fill(CFG);
-  static constexpr bool ONE_ADV = MXA_ONE_ADVANCE != 0 && mxa_cfg::one_advance(CFG);
-  typedef typename std::conditional<TFILL, RSt<BUILD, (!BUILD || MXA_BUILD_WINDOWS != 0) ? RS_WIN : RS_HBM, true>,
-                                    RSt<BUILD>>::type RS;
+  // RNG stream handles.  TFILL (MXA_TEMPER_FILL_MASK): the windows keep tempered outputs (the four
+  // xor-shift steps run once per fill, 64 lanes wide on the VALU) and a draw is the LDS read alone;
+  // elsewhere a window holds the state words and every draw tempers its word on the scalar unit
+  // (DESIGN.md Appendix R.12).  A unit with the tempered fill knows at compile time how each stream
+  // reads: G/O/K/L (RS) through their windows, an agent's own stream (ARS, Agent.random_state)
+  // from HBM.  Every other unit keeps the one handle type whose draws test the window pointer
+  // (RS_PTR): its code is the code it was measured with.  The build kernel draws through windows
+  // too (one coalesced 64-word fill instead of a dependent load per word): G/O/K/L their
+  // run-kernel windows, an agent stream the L window (the build never draws from L)
+  static constexpr bool TFILL = mxa_cfg::temper_fill(CFG);
+  // ONE_ADV (MXA_ONE_ADVANCE_MASK): o_observe clamps the time and calls o_advance once; elsewhere
+  // one call per side of the clamp, which inlines the oracle's advance twice into every
+  // value_place (Appendix R.12)
+  static constexpr bool ONE_ADV = mxa_cfg::one_advance(CFG);
+  typedef typename std::conditional<TFILL, RSt<BUILD, RS_WIN, true>, RSt<BUILD>>::type RS;
   typedef typename std::conditional<BUILD || !TFILL, RS, RSt<false, RS_HBM, true>>::type ARS;
   // variate tables (mxa_config.h MXA_VARIATE_*_MASK): the oracle stream's in LDS, dropped at every
   // launch start like the stream windows; one per value agent in the env block (Layout::off_vt),
@@ -1112,6 +1069,13 @@ struct Eng {
 #ifdef MXA_PROF
   LDSP u64* prof;
 #endif
+  // a kernel's last statement: this env's phase counters into the device totals (MXA_PROF builds)
+  DEV void prof_flush() {
+#ifdef MXA_PROF
+    atomicAdd(&g_mxa_prof[lane], (unsigned long long)prof[lane]);
+    atomicAdd(&g_mxa_prof[64 + lane], (unsigned long long)prof[64 + lane]);
+#endif
+  }
   LDSP u64* hotrec;  // [HOT][64]: the exchange's (and the market maker's or replay agent's) agent record
   // the exchange's latency row in LDS for the launch (MXA_LAT_LDS_MASK): every send reads one
   // entry, which from HBM is a dependent memory round trip on the event chain
@@ -1300,7 +1264,7 @@ struct Eng {
   // agent RNG stream (Agent.random_state): key words in HBM, pos/gauss cache in the record
   DEV ARS agent_rs() {
     ARS r;
-    r.lw = BUILD && MXA_BUILD_WINDOWS ? rwin + 3 * 64 : nullptr;
+    r.lw = BUILD ? rwin + 3 * 64 : nullptr;
     r.lw0 = r.lwn = 0;
     r.key = rng_key(4 + cur_agent);
     r.p = rgi(AF_RS_POS);
@@ -1332,11 +1296,10 @@ struct Eng {
     r.m = h.rs_m[s];
     r.hasg = h.rs_has_gauss[s];
     r.gauss = h.rs_gauss[s];
+    r.lw = rwin + s * 64;
     if constexpr (BUILD) {  // an empty window: the first draw fills it
-      r.lw = MXA_BUILD_WINDOWS ? rwin + s * 64 : nullptr;
       r.lw0 = r.lwn = 0;
     } else {
-      r.lw = rwin + s * 64;
       r.lw0 = h.rs_w0[s];
       r.lwn = h.rs_wn[s];
     }
@@ -1711,10 +1674,11 @@ struct Eng {
   static constexpr bool MAXQ_REG = !BUILD && (((MXA_MAXQ_REG_MASK) >> CFG) & 1);
   static constexpr bool TVB = ((MXA_TV_BLOCKS_MASK) >> CFG) & 1;
   i32 maxq;
-  DEV void note_max_q() {
-    if constexpr (MAXQ_REG) maxq = qcount > maxq ? qcount : maxq;
-    else if (qcount > h.max_q) h.max_q = qcount;
+  DEV void note_max_q(int n) {
+    if constexpr (MAXQ_REG) maxq = n > maxq ? n : maxq;
+    else if (n > h.max_q) h.max_q = n;
   }
+  DEV void note_max_q() { note_max_q(qcount); }
   DEV void q_push(u64 key, u32 seq, const Msg& m) {
     PROF_SCOPE(65);
     QM use = qfree;
@@ -4094,7 +4058,7 @@ struct Eng {
   // price qty oid dense meta arrival prev next idprev idnext), 10/11 the level's quantity (lo,
   // hi), 12 the level's count, 13 free_top, 14/15 the side's level count and best
   DEV i32 rp_gather(int side, i32 x, i32 e) {
-    RPCHK(e >= 0 && e < U(rx->L.C) && x >= 0 && x < U(rx->L.P), "rp_unlink entry/level", (i64)e * 100000 + x);
+    RPCHK(e >= 0 && e < U(rx->L.C) && x >= 0 && x < U(rx->L.P), "rp_unlink entry/level", (i64)e * 100000 + x, 0);
     const u64 sx = (u64)side * (u32)rx->L.P + (u32)x;
     const u64 o_w = rx->L.off_pool + (u64)e * sizeof(RpEntry), o_c = rx->L.off_lvc + 4 * sx, o_q = rx->L.off_lvq + 8 * sx,
               o_rh = rx->L.off_rh;
@@ -4119,7 +4083,7 @@ struct Eng {
     const i32 q = rdli(g, 1), d = rdli(g, 3), p = rdli(g, 6), n = rdli(g, 7), ip = rdli(g, 8), in = rdli(g, 9);
     const i32 cnt = rdli(g, 12), top = rdli(g, 13), nl = rdli(g, 14), b = rdli(g, 15);
     RPCHK(p >= -1 && p < U(rx->L.C) && n >= -1 && n < U(rx->L.C) && d >= 0 && d < U(rx->L.D) && top >= 0 && top < U(rx->L.C),
-          "rp_unlink links", (i64)p * 1000000 + n);
+          "rp_unlink links", (i64)p * 1000000 + n, 0);
     {  // every lane stores the same (uniform) value
       if (p >= 0) E[p].next = n;
       else lv_head(side)[x] = n;
@@ -5411,14 +5375,13 @@ struct Eng {
   // else (another event before the bound, stopTime or the close behind t, a launch budget that
   // cuts the group, a queue without two free slots, a market maker that waits for the spread alone, a
   // volume query that would raise) takes the queued path unchanged.
-  static constexpr bool SYNCQ_BASE = !BUILD && RUNS && !BLOG && !MD && !RP && !TIER && PC.ex_pipeline == 0;
-  static constexpr bool SYNCQ = SYNCQ_BASE && ((((MXA_SYNC_QUERY_MASK)) >> CFG) & 1) && PC.n_mm > 0;
+  static constexpr bool INPLACE = !BUILD && RUNS && !BLOG && !MD && !RP && !TIER && PC.ex_pipeline == 0 &&
+                                  (((MXA_INPLACE_MASK) >> CFG) & 1);
+  static constexpr bool SYNCQ = INPLACE && PC.n_mm > 0;
   // "Nothing else pending" for a group of cur_agent's at t.  The group's pops carry keys (t, 0,
   // MESSAGE) and (t, cur_agent, MESSAGE); a pending event whose key is not below (t, cur_agent + 1)
   // sorts after all of them whatever its seq, and touches nothing before it pops (DESIGN.md §3 "The
-  // bound").  The agent's own wakeup at t, (t, cur_agent, WAKEUP), is below the bound.  Without the
-  // mask bit: no pending event with time <= t at all.
-  static constexpr bool SYNCB = ((((MXA_SYNC_BOUND_MASK)) >> CFG) & 1) != 0;
+  // bound").  The agent's own wakeup at t, (t, cur_agent, WAKEUP), is below the bound.
   // an in-place group of kind k was taken (instrumented runs: mxa_read_inplace)
   DEV void note_inplace(int k) {
     if constexpr (INSTR && !BUILD) {
@@ -5426,7 +5389,7 @@ struct Eng {
     }
   }
   DEV bool none_before(i64 t) {
-    const u64 bound = SYNCB ? (((u64)t << KSH) | ((u64)(cur_agent + 1) << 2)) : ((u64)(t + 1) << KSH);
+    const u64 bound = ((u64)t << KSH) | ((u64)(cur_agent + 1) << 2);
     return bal(mk < bound) == 0;
   }
   // ---------------- the market maker's cancel and ladder runs in place
@@ -5450,9 +5413,8 @@ struct Eng {
   // whose order no longer rests; a launch budget or a queue too small for the whole group; a
   // ladder mm_requote would place order by order; a ladder order that could match or overflow the
   // book as the cancels leave it.
-  static constexpr bool LADDER_RQ = MXA_LADDER_REPLIES_QUEUED != 0;
   static constexpr int MM_CNL = 2 * ((int)PC.mm_ticks + 1);
-  static constexpr bool SYNCL = SYNCQ && ((((MXA_SYNC_LADDER_MASK)) >> CFG) & 1) && !PC.mm_rt && BATCH && !TIER && MM_CNL <= 64;
+  static constexpr bool SYNCL = SYNCQ && !PC.mm_rt && BATCH && !TIER && MM_CNL <= 64;
   // mm_requote(mid) at the volume reply of mm_cycle; returns the pops handled in place (0: queued).
   // budget: as mm_cycle's
   DEV int mm_ladder_cycle(i64 t, i64 mid, i64 budget) {
@@ -5494,7 +5456,7 @@ struct Eng {
       o.price = me ? d : o.price;
     }
     bool ok = nc <= 64 && (nc == 0 || first >= 2) && sz > 0 && nord + CNL <= PC.L.open_cap && nc + CNL <= PC.L.open_cap &&
-              budget >= 5 + (LADDER_RQ ? 1 : 2) * (nc + CNL) && qcount + nc + CNL + 1 <= QCAP && lb >= 0 && la + PC.mm_ticks <= INT32_MAX;
+              budget >= 5 + 2 * (nc + CNL) && qcount + nc + CNL + 1 <= QCAP && lb >= 0 && la + PC.mm_ticks <= INT32_MAX;
     int hit[SO];
     if (ok) ok = ex_cancel_find(mem, o.oid, o.price, o.is_buy, hit);
     if (ok) {
@@ -5563,9 +5525,9 @@ struct Eng {
     if (mem) {
       if (cmp) {
         OpenOrder d = o;
-        if constexpr (!LADDER_RQ) d.oid = -1;
+        d.oid = -1;
         oo[lane] = d;
-      } else if constexpr (!LADDER_RQ) {
+      } else {
         oo[pos].oid = -1;
       }
     }
@@ -5579,20 +5541,11 @@ struct Eng {
     }
     rs(AF_NUSED, (u32)(u2 + CNL));
     // the queue: its peak, the seqs, the next wakeup
-    const int hw = qcount + nc + CNL + 1;
-    if constexpr (MAXQ_REG) maxq = hw > maxq ? hw : maxq;
-    else if (hw > h.max_q) h.max_q = hw;
+    note_max_q(qcount + nc + CNL + 1);
     const u32 s = seq;
     fl_set(FL_AW_SPREAD, true);
     fl_set(FL_AW_TV, true);
     q_push_at(wl, wj, ((u64)(t + mm_wake()) << KSH) | ((u64)cur_agent << 2) | MT_WAKEUP, s + (u32)(nc + CNL), msg_make(MK_WAKEUP, 0));
-    if constexpr (LADDER_RQ) {  // the measured variant: the replies go through the queue as runs
-      rs(AF_NORD, (u32)(nord + CNL));
-      seq = s + (u32)(nc + CNL + 1);
-      q_push_lanes(mem, kmm, rc);
-      q_push_lanes(act, kmm, lm);
-      return nc + CNL;
-    }
     // ORDER_CANCELLED x nc (the book's quantity and owner), ORDER_ACCEPTED x CNL at the market maker
     run_account(kmm, t, rc, nc);
     if (INSTR && (hash_on || trace) && lane == 0 && nc > 0) h.kc[MXA_KC_REC]++;  // the ORDER_CANCELLED run's rec_load
@@ -5636,8 +5589,7 @@ struct Eng {
       pops += 2;
     }
     seq += 4;
-    if constexpr (MAXQ_REG) maxq = qcount + 2 > maxq ? qcount + 2 : maxq;
-    else if (qcount + 2 > h.max_q) h.max_q = qcount + 2;
+    note_max_q(qcount + 2);
     atime_store(0, t);
     i64 mid;
     const Msg rs_ = ex_spread_reply(1, false);
@@ -5659,26 +5611,20 @@ struct Eng {
   // QUERY_SPREAD at the exchange, then ORDER_CANCELLED (if the order still rested: del orders[id],
   // the fast path of the event loop) and the spread reply at the agent, whose handler places the
   // new order.  A LIMIT_ORDER that can cross is sent as an event (it fans out executions); one that
-  // rests is taken here with its ORDER_ACCEPTED (value_order below, MXA_SYNC_ORDER_MASK).
+  // rests is taken here with its ORDER_ACCEPTED (value_order below).
   // More than one open order, or a list longer than one 64-entry chunk, takes the queued path.
-  static constexpr bool SYNCV = SYNCQ_BASE && ((((MXA_SYNC_VALUE_MASK)) >> CFG) & 1) && PC.n_value > 0;
+  static constexpr bool SYNCV = INPLACE && PC.n_value > 0;
   DEV int value_cycle(i64 t, i64 budget) {
     // the open-order chunk needs only cur_agent and AF_NUSED, which the head of the wakeup leaves as
     // they are (it draws the next wake time and pushes the wakeup; the list changes at orders and
-    // acknowledgements only): MXA_VALUE_OPEN_EARLY issues its load before the head's dependent
-    // stream read instead of after it.  A load wasted on a wakeup that ends in its head is harmless
+    // acknowledgements only).  Issuing its load before the head's dependent stream read was
+    // measured and lost: it is loaded after the head
     OpenOrder o;
     o.oid = -1;
     o.is_buy = o.qty = o.price = 0;
-    if constexpr (MXA_VALUE_OPEN_EARLY != 0) {
-      const i32 u0 = rgi(AF_NUSED);
-      if (lane < u0 && u0 <= 64) o = open_ptr(cur_agent)[lane];
-    }
     if (!value_wake_head()) return 0;
     const i32 u = rgi(AF_NUSED), k = rgi(AF_NORD);
-    if constexpr (MXA_VALUE_OPEN_EARLY == 0) {
-      if (lane < u && u <= 64) o = open_ptr(cur_agent)[lane];
-    }
+    if (lane < u && u <= 64) o = open_ptr(cur_agent)[lane];
     const u64 live = bal(o.oid != -1);
     const bool ok = status == ST_RUNNING && cur_agent < ACK_LIMIT && t <= PC.mkt_close && t <= stop_t && k <= 1 && u <= 64 &&
                     __popcll(live) == k && budget >= 3 + 2 * k && qcount + k + 1 <= QCAP &&
@@ -5712,8 +5658,7 @@ struct Eng {
     atime_store(0, t);
     const int np = k + 2 + (found ? 1 : 0);
     seq += (u32)np;
-    if constexpr (MAXQ_REG) maxq = qcount + k + 1 > maxq ? qcount + k + 1 : maxq;
-    else if (qcount + k + 1 > h.max_q) h.max_q = qcount + k + 1;
+    note_max_q(qcount + k + 1);
     if (found) {  // ORDER_CANCELLED at the agent: del self.orders[id]
       account_pop(t, kag, cr);
       del_open(idx);
@@ -5723,9 +5668,7 @@ struct Eng {
     if (instr && lane == 0) h.kc[MXA_KC_REC] += found ? 2 : 1;  // the replies' record round trips
     rs(AF_STATE, AS_AWAITING_SPREAD);
     if (MXA_RARE(dirty)) rng_maint();  // the wakeup's own event boundary, before the reply's draws
-    if constexpr (SYNCO) return np + value_receive<true>(r, budget - 1 - np);
-    value_receive(r);
-    return np;
+    return np + value_receive<true>(r, budget - 1 - np);
   }
   // ---------------- the value agent's resting order and its acknowledgement in place
   // The reply's handler ends value_cycle's group by placing the agent's one order: a LIMIT_ORDER at
@@ -5750,9 +5693,6 @@ struct Eng {
   // The queue's high-water mark needs no update: when the queued sequence pushes the order, the
   // group's k + 1 earlier messages have all been popped, so it holds qcount + 1 events, and
   // again qcount + 1 with the ORDER_ACCEPTED; value_cycle took the peak qcount + k + 1 at its head.
-  // MXA_ORDER_ACK_QUEUED: the measured variant whose ORDER_ACCEPTED is still pushed and popped.
-  static constexpr bool SYNCO = SYNCV && ((((MXA_SYNC_ORDER_MASK)) >> CFG) & 1);
-  static constexpr bool ORDER_AQ = MXA_ORDER_ACK_QUEUED != 0;
   DEV int value_order(i64 qty, int is_buy, i32 price, bool rests, i64 room) {
     const i64 oid = next_order_id();
     const i32 n = rgi(AF_NORD), u = rgi(AF_NUSED);
@@ -5778,14 +5718,13 @@ struct Eng {
     const Msg am = msg_order(MK_ACCEPTED, (i32)oid, cur_agent, is_buy, (i32)qty, price, 0);
     if (INSTR && (hash_on || trace)) {
       account_pop(cur, ((u64)cur << KSH) | MT_MESSAGE, msg_order(MK_LIMIT, (i32)oid, cur_agent, is_buy, (i32)qty, price, 0));
-      if constexpr (!ORDER_AQ) account_pop(cur, kag, am);
+      account_pop(cur, kag, am);
     } else {
-      pops += ORDER_AQ ? 1 : 2;
+      pops += 2;
     }
-    if constexpr (ORDER_AQ) q_push(kag, seq + 1, am);
     seq += 2;
     ex_limit_book(lane == 0, is_buy, price, (i32)oid, cur_agent, (i32)qty);
-    return ORDER_AQ ? 1 : 2;
+    return 2;
   }
 
   DEV void run(i64 max_pops) {
@@ -6057,7 +5996,7 @@ struct Builder : Eng<CFG, true> {
   // expand every stream's init_genrand in parallel (lane = stream).  With room in the LDS queue
   // area (empty until the kernelStarting wakeups) each lane's 16-word runs go through an LDS tile
   // and leave as 64-byte runs of 4 streams per store instead of 64 scattered dwords.
-  static constexpr bool SEED_TILE = MXA_SEED_TILE && E::LDS_Q >= 64 * 17 * 4;
+  static constexpr bool SEED_TILE = E::LDS_Q >= 64 * 17 * 4;
   DEV void seed_streams(int first) {
     const MxaParams& P = E::PC;
     wfence();
@@ -6399,12 +6338,11 @@ struct Builder : Eng<CFG, true> {
         set_seed(4 + a, g_seed(G));
         i64 size = rs_randint(G, 20, 50);
         rec_init(a, AG_NOISE);
-        if constexpr (MXA_WAKE_LANES) this->rsd(AF_WAKEUP_TIME, u);
-        else this->rs64(AF_WAKEUP_TIME, wake_time_of(u, P.noise_open, P.noise_close));
+        this->rsd(AF_WAKEUP_TIME, u);
         this->rs(AF_SIZE, (u32)size);
         this->rec_store();
       }
-      if constexpr (MXA_WAKE_LANES) wake_times_lanes();
+      wake_times_lanes();
       for (int a = P.first_value; a < P.first_value + P.n_value; a++) {
         set_seed(4 + a, g_seed(G));
         i64 size = rs_randint(G, 20, 50);
@@ -6616,7 +6554,7 @@ struct Builder : Eng<CFG, true> {
       this->agent_rs_put(A);
       this->rec_store();
     }
-    constexpr bool ZI_LANES = MXA_ZI_THETA_LANES && E::PC.n_zi + E::PC.n_hbl > 0;
+    constexpr bool ZI_LANES = E::PC.n_zi + E::PC.n_hbl > 0;
     if constexpr (ZI_LANES) zi_theta_lanes();
     for (int a = P.first_zi; a < P.first_zi + P.n_zi + P.n_hbl; a++) {  // HBL agents are ZI subclasses
       if (ZI_LANES && !zi_fallback(a)) continue;  // done by zi_theta_lanes
@@ -6646,17 +6584,7 @@ struct Builder : Eng<CFG, true> {
       rs_maint(r);
       this->grs_put(k, r);
     }
-    if constexpr (MXA_MAINT_LANES) {
-      maint_agents();
-    } else {
-      for (int a = 0; a < n; a++) {
-        this->rec_load(a);
-        ARS A = this->agent_rs();
-        rs_maint(A, MXA_AGENT_LA);
-        this->agent_rs_put(A);
-        this->rec_store();
-      }
-    }
+    maint_agents();
     // Kernel.runner: kernelInitializing (exchange opening price = r_bar, a python float; with the
     // ExternalFileOracle int(round(price at the open)), ExternalFileOracle.py:37-50),
     // kernelStarting (every agent wakes at startTime, in id order)
@@ -6724,10 +6652,7 @@ __global__ __launch_bounds__(64, mxa_cfg::shape(CFG).waves) void mxa_run_kernel(
   g.load();
   g.run(max_pops);
   g.save();
-#ifdef MXA_PROF
-  atomicAdd(&mxa::g_mxa_prof[g.lane], (unsigned long long)g.prof[g.lane]);
-  atomicAdd(&mxa::g_mxa_prof[64 + g.lane], (unsigned long long)g.prof[64 + g.lane]);
-#endif
+  g.prof_flush();
 }
 
 template <int CFG, bool LOG>
@@ -6791,10 +6716,7 @@ __global__ __launch_bounds__(64, mxa_cfg::shape(CFG).waves) void mxa_step_kernel
     if (g.lane == 0) flags[row] = done | (hobs ? 2 : 0) | (g.status == ST_ERROR ? 4 : 0);
   }
   if (MANY) g.save();
-#ifdef MXA_PROF
-  atomicAdd(&mxa::g_mxa_prof[g.lane], (unsigned long long)g.prof[g.lane]);
-  atomicAdd(&mxa::g_mxa_prof[64 + g.lane], (unsigned long long)g.prof[64 + g.lane]);
-#endif
+  g.prof_flush();
 }
 
 // The closed-loop flavour (include/mxa.h mxa_step_policy): k_steps periods per launch as MANY, the
@@ -6865,10 +6787,7 @@ __global__ __launch_bounds__(64, mxa_cfg::shape(CFG).waves) void mxa_step_policy
     if (pol.state != nullptr) g.rl_state_row(pol.state + (size_t)MXA_RL_STATE_WORDS * row);
   }
   g.save();
-#ifdef MXA_PROF
-  atomicAdd(&mxa::g_mxa_prof[g.lane], (unsigned long long)g.prof[g.lane]);
-  atomicAdd(&mxa::g_mxa_prof[64 + g.lane], (unsigned long long)g.prof[64 + g.lane]);
-#endif
+  g.prof_flush();
 }
 #endif
 
@@ -6923,7 +6842,7 @@ __global__ __launch_bounds__(64) void mxa_variate_probe_kernel(uint32_t seed, co
       double v;
       if (pass == 0) mxa::rs_maint(r, MXA_AGENT_LA);  // the engine's look-ahead at an event boundary
       if (kind == 0) v = pass == 0 ? mxa::vt_draw_exponential(r, tab, d, 1.0, put, none, cap) : mxa::rs_exponential(r, 1.0);
-      else if (kind == 1) v = pass == 0 ? mxa::vt_draw_gauss<true>(r, tab, d, put, none, cap) : mxa::rs_gauss_serial(r);
+      else if (kind == 1) v = pass == 0 ? mxa::vt_draw_gauss<true>(r, tab, d, put, none, cap) : mxa::rs_gauss(r);
       else if (kind == 2) v = (double)mxa::rs_u32(r);
       else v = (double)mxa::rs_randint(r, 0, 100);
       if (__lane_id() == 0) {

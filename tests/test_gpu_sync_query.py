@@ -5,7 +5,7 @@ order counter, last trade, every agent's cash / holdings / open orders) at the e
 in-place path: a launch budget that cuts the group at every position, stopTime at, before and
 after a market-maker wake, an instant the momentum agents share with the market maker (the
 queued fallback), a value agent waking with an open order, the step kernel, and a configuration
-outside MXA_SYNC_QUERY_MASK."""
+outside MXA_INPLACE_MASK."""
 import numpy as np
 import pytest
 import torch  # before libmxa loads: one HIP runtime per process (the step kernel's device buffers)

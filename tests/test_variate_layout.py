@@ -2,7 +2,7 @@
 from the header's constants by the host compiler as test_lib_exports.py checks the layout: a
 configuration outside the masks has no table bytes and the block and LDS sizes it had before the
 tables existed, rmsc03 has one table per value agent between the market-data slots and the trace
-and the oracle stream's table in LDS, and with the global switch off nobody has any."""
+and the oracle stream's table in LDS, and with both masks 0 nobody has any."""
 import os
 import subprocess
 
@@ -54,7 +54,7 @@ def test_global_switch_off_leaves_no_table_anywhere(tmp_path):
     lines = []
     for c in sorted(BEFORE):
         lines += _unchanged(c)
-    _compile(tmp_path, lines, "-DMXA_VARIATE_TABLES=0")
+    _compile(tmp_path, lines, "-DMXA_VARIATE_O_MASK=0", "-DMXA_VARIATE_AGENT_MASK=0")
 
 
 def test_each_mask_alone(tmp_path):

@@ -1,10 +1,12 @@
 #!/bin/bash
 # build rmsc03-only libmxa variants: NAME:SRCROOT:FLAGS...   (SRCROOT "." = working tree)
-# the in-place parts one by one, each on top of the previous ones:
-#   "q:.:-DMXA_SYNC_VALUE_MASK=0 -DMXA_SYNC_LADDER_MASK=0 -DMXA_SYNC_BOUND_MASK=0"   mm_cycle alone
-#   "v:.:-DMXA_SYNC_LADDER_MASK=0 -DMXA_SYNC_BOUND_MASK=0"                           + value_cycle
-#   "l:.:-DMXA_SYNC_BOUND_MASK=0"                                                    + the ladder group
-#   "b:.:"                                                                           + the tighter bound (shipped)
+# FLAGS are the per-configuration masks and the capacities of mxa_config.h / mxa_kernels.hip, and
+# -DMXA_ONLY_CFG=<id> for a configuration other than rmsc03 (id 0), for example:
+#   "b:.:"                                                   the shipped build
+#   "q:.:-DMXA_INPLACE_MASK=0"                               every exchange round trip through the queue
+#   "w:.:-DMXA_TEMPER_FILL_MASK=0 -DMXA_ONE_ADVANCE_MASK=0"  state words in the stream windows
+#   "t:.:-DMXA_VARIATE_O_MASK=0 -DMXA_VARIATE_AGENT_MASK=0"  serial draws, no variate tables
+#   "p:/path/to/a/checkout:"                                 another source tree (an A/B parent)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 pids=()
