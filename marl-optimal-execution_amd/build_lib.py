@@ -41,7 +41,7 @@ CFG_FLAGS = {1: ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], 2: ["-fno-slp-vect
 
 
 def sources():
-    return [os.path.join(HERE, "csrc", d) for d in DEPS] + [os.path.join(ROOT, "include", h) for h in ("mxa.h", "mxa_snap.h", "mxa_depth.h", "mxa_bars.h", "mxa_variates.h")]
+    return [os.path.join(HERE, "csrc", d) for d in DEPS] + [os.path.join(ROOT, "include", h) for h in ("mxa.h", "mxa_snap.h", "mxa_depth.h", "mxa_bars.h", "mxa_variates.h", "mxa_policy_features.h", "mxa_state_spec.h")]
 
 
 def build_id(extra=()):
@@ -93,24 +93,31 @@ def build(force=False, verbose=True, jobs=None):
 
 
 DDQN_SRCS = [os.path.join(HERE, "csrc", f) for f in ("ddqn_period.hip", "ddqn_qnet.hip", "ddqn_train.hip")]
-DDQN_DEPS = DDQN_SRCS + [os.path.join(HERE, "csrc", "ddqn_device.h"), os.path.join(HERE, "csrc", "ddqn_qnet_device.h"),
-                         os.path.abspath(__file__)]
+DDQN_FEATURES_SRCS = [os.path.join(HERE, "csrc", "ddqn_features.hip")]
+DDQN_DEPS = DDQN_SRCS + DDQN_FEATURES_SRCS + [os.path.join(HERE, "csrc", f) for f in
+                                              ("ddqn_device.h", "ddqn_qnet_device.h", "ddqn_period_kernels.h")] + \
+    [os.path.join(ROOT, "include", "mxa_state_spec.h"), os.path.abspath(__file__)]
 DDQN_OUT = os.path.join(HERE, "lib", "libmxa_ddqn.so")
+DDQN_FEATURES_OUT = os.path.join(HERE, "lib", "libmxa_ddqn_features.so")
 
 
 def build_ddqn(force=False, verbose=True):
     """libmxa_ddqn.so (include/mxa_ddqn.h, mxa_ddqn_train.h): the DDQN learner's kernels (mxabides.ddqn), the
     per-period bookkeeping of run_episode, the Q-network forward and epsilon-greedy action of
     DDQNLearner(fused_act=True) and the update of DDQNLearner(fused_learn=True); a library of its own,
-    outside the engine's build id"""
-    if not force and os.path.exists(DDQN_OUT) and os.path.getmtime(DDQN_OUT) >= max(map(os.path.getmtime, DDQN_DEPS)):
-        return DDQN_OUT
-    os.makedirs(os.path.dirname(DDQN_OUT), exist_ok=True)
-    cmd = [HIPCC] + FLAGS + DDQN_SRCS + ["-o", DDQN_OUT + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    os.replace(DDQN_OUT + ".tmp", DDQN_OUT)
+    outside the engine's build id.  With it libmxa_ddqn_features.so (include/mxa_ddqn_features.h): the
+    per-period kernels for a state of N features, beside it so that libmxa_ddqn.so's exports stay
+    those of its two headers"""
+    newest = max(map(os.path.getmtime, DDQN_DEPS))
+    for srcs, out in ((DDQN_SRCS, DDQN_OUT), (DDQN_FEATURES_SRCS, DDQN_FEATURES_OUT)):
+        if not force and os.path.exists(out) and os.path.getmtime(out) >= newest:
+            continue
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        cmd = [HIPCC] + FLAGS + srcs + ["-o", out + ".tmp"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+        os.replace(out + ".tmp", out)
     return DDQN_OUT
 
 

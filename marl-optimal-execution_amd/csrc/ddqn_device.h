@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "../../include/mxa_state_spec.h"
+
 // torch.bucketize(x, bd, right=True): searchsorted's upper bound, NaN sorting last
 __device__ inline int64_t upper_bound(double x, const double* bd, int n) {
   int64_t lo = 0, hi = n;
@@ -25,6 +27,25 @@ __device__ inline void state_of(const double* o, const double* g0, int n0, const
   const double qr = 2.0 * (o[1] / q0) - 1.0;
   out[0] = (float)upper_bound(tr, g0, n0);
   out[1] = (float)upper_bound(qr, g1, n1);
+}
+
+// One feature of a state spec (include/mxa_state_spec.h) on the observation row o: the scaled column,
+// binned on the feature's own split points, or passed through where it has none.  With
+// -ffp-contract=off the default spec's 2.0 * (o / nh) + (-1.0) is state_of's 2.0 * (o / nh) - 1.0.
+// O: a pointer to the row in any address space (the step kernel's observation lives in LDS)
+template <class O>
+__device__ inline float state_feature(O o, const mxa_state_spec& sp, int f) {
+  const double x = sp.mul[f] * (o[sp.col[f]] / sp.div[f]) + sp.add[f];
+  const int n = sp.goff[f + 1] - sp.goff[f];
+  return n > 0 ? (float)upper_bound(x, sp.grid + sp.goff[f], n) : (float)x;
+}
+
+// ExecutionTask(features=...).state of one env: out[f] for f < n_feat (out holds
+// MXA_STATE_MAX_FEATURES; the constant trip count keeps it in registers)
+__device__ inline void state_of_spec(const double* o, const mxa_state_spec& sp, float* out) {
+#pragma unroll
+  for (int f = 0; f < MXA_STATE_MAX_FEATURES; f++)
+    if (f < sp.n_feat) out[f] = state_feature(o, sp, f);
 }
 
 // ExecutionTask.actions of one env: the action table's row t, or on the horizon's last step

@@ -928,6 +928,26 @@ int mxa_step_policy(mxa_handle* h, int32_t k, int32_t first_zero, const mxa_poli
                      (int)(first_zero != 0));
 }
 
+// mxa_step_policy with the state of a spec (include/mxa_policy_features.h): every refusal carries
+// its message and comes before the first HIP call
+int mxa_step_policy_spec(mxa_handle* h, int32_t k, int32_t first_zero, const mxa_policy* p, const mxa_state_spec* spec,
+                         double* d_obs, int32_t* d_flags, int64_t* d_a, double* d_act, double* d_state) {
+  static const char* const fn = "mxa_step_policy_spec";
+  if (!h) return refuse(nullptr, fn, "null handle");
+  if (!h->gym) return refuse(h, fn, "not a GymKernel handle");
+  if (k <= 0) return refuse(h, fn, "k <= 0");
+  if (!p || !d_obs || !d_flags || !d_a || !d_act) return refuse(h, fn, "a null policy or output array");
+  if (!p->params || !p->table) return refuse(h, fn, "null parameters or action table");
+  if (!p->test && (!p->u || !p->rnd || !p->eps)) return refuse(h, fn, "train mode with a null u, rnd or eps");
+  if (!qwave::dims_ok(p->n_layers, p->dims)) return refuse(h, fn, "dimensions outside 1..8 layers of 1..256 units");
+  if (const char* why = mxa_state_spec_refusal(spec, 9)) return refuse(h, fn, why);
+  if (p->dims[0] != spec->n_feat) return refuse(h, fn, "dims[0] != n_feat");
+  if (d_state && h->P.n_rl != 1) return refuse(h, fn, "an rl-state array on a handle without one execution agent");
+  if (!h->e.step_policy_spec) return refuse(h, fn, "the library was built without the step kernels");
+  return step_launch(h, h->e.step_policy_spec, h->e.step_policy_spec_fast, *p, *spec, d_obs, d_flags, d_a, d_act,
+                     d_state, (int)k, (int)(first_zero != 0));
+}
+
 // the same with device arrays (e.g. torch tensors), asynchronous on the handle's stream
 int mxa_step_device(mxa_handle* h, const double* d_actions, double* d_obs, int32_t* d_flags) {
   if (!h || !h->gym) return MXA_EINVAL;

@@ -26,6 +26,11 @@ typedef void (*mxa_step_many_fn)(dim3, dim3, size_t, hipStream_t, char*, uint64_
 typedef void (*mxa_step_policy_fn)(dim3, dim3, size_t, hipStream_t, char*, uint64_t, int, int, int64_t, const RpCtx*,
                                    const mxa_policy&, double*, int32_t*, int64_t*, double*, double*, int, int);
 
+// the same with the state of a spec (mxa_step_policy_spec): the spec by value after the policy
+typedef void (*mxa_step_policy_spec_fn)(dim3, dim3, size_t, hipStream_t, char*, uint64_t, int, int, int64_t, const RpCtx*,
+                                        const mxa_policy&, const mxa_state_spec&, double*, int32_t*, int64_t*, double*,
+                                        double*, int, int);
+
 typedef int (*mxa_inplace_fn)(uint64_t*);  // read and clear the configuration's in-place group counts (mxa_read_inplace)
 typedef int (*mxa_occ_fn)(size_t);  // resident blocks (envs) per CU of the measured kernel at that LDS size
 
@@ -37,6 +42,7 @@ struct MxaEntry {
   mxa_step_fn step, step_fast; // GymKernel configurations (step_fast: without the instrumentation)
   mxa_step_many_fn step_many, step_many_fast;  // k steps per launch, actions given up front
   mxa_step_policy_fn step_policy, step_policy_fast;  // k periods per launch, the Q-network policy in place
+  mxa_step_policy_spec_fn step_policy_spec, step_policy_spec_fast;  // the same, the state from a spec
   mxa_inplace_fn inplace;      // g_mxa_inplace of the configuration's translation unit
   mxa_occ_fn occ;              // hipOccupancyMaxActiveBlocksPerMultiprocessor of run_fast / step_fast
 };

@@ -46,6 +46,15 @@ void launch_step_policy(dim3 g, dim3 b, size_t lds, hipStream_t s, char* base, u
   hipLaunchKernelGGL((mxa_step_policy_kernel<CFG, INSTR>), g, b, lds, s, base, stride, n, tcap, max_pops, ctx, pol, obs,
                      flags, k);
 }
+template <int CFG, bool INSTR>
+void launch_step_policy_spec(dim3 g, dim3 b, size_t lds, hipStream_t s, char* base, uint64_t stride, int n, int tcap,
+                             int64_t max_pops, const RpCtx* ctx, const mxa_policy& p, const mxa_state_spec& spec,
+                             double* obs, int32_t* flags, int64_t* a, double* act, double* state, int k,
+                             int first_zero) {
+  MxaStepPolicySpec ps{{p, first_zero, a, act, state}, spec};
+  hipLaunchKernelGGL((mxa_step_policy_spec_kernel<CFG, INSTR>), g, b, lds, s, base, stride, n, tcap, max_pops, ctx, ps,
+                     obs, flags, k);
+}
 #endif
 
 template <int CFG, bool GYM>
@@ -98,6 +107,8 @@ MxaEntry make_entry() {
     e.step_many_fast = launch_step_many<CFG, false>;
     e.step_policy = launch_step_policy<CFG, true>;
     e.step_policy_fast = launch_step_policy<CFG, false>;
+    e.step_policy_spec = launch_step_policy_spec<CFG, true>;
+    e.step_policy_spec_fast = launch_step_policy_spec<CFG, false>;
   }
 #endif
   return e;

@@ -6789,6 +6789,79 @@ __global__ __launch_bounds__(64, mxa_cfg::shape(CFG).waves) void mxa_step_policy
   g.save();
   g.prof_flush();
 }
+
+// The closed-loop flavour with a state of N features (include/mxa_policy_features.h
+// mxa_step_policy_spec): mxa_step_policy_kernel with the network's input row made by
+// state_feature (ddqn_device.h) from whichever columns of the env's stored observation the spec
+// names, bit for bit the per-step sequence mxa_ddqn_state_spec, mxa_qnet_act, mxa_step_device,
+// mxa_write_rl_state.  Every lane computes every feature in a loop whose trip count and spec fields
+// are wave-uniform (the fields stay scalar loads of the kernel arguments; a feature per lane would
+// index the by-value spec with a lane-varying f), and feature f is kept on lane f, where
+// qwave::forward reads input f.  A second kernel that restates the loop body, for the reason given
+// above: the other step kernels keep their instructions.
+struct MxaStepPolicySpec {
+  MxaStepPolicy pol;
+  mxa_state_spec spec;
+};
+template <int CFG, bool INSTR>
+__global__ __launch_bounds__(64, mxa_cfg::shape(CFG).waves) void mxa_step_policy_spec_kernel(
+    char* base, uint64_t stride, int n_envs, int trace_cap, int64_t max_pops, const RpCtx* ctx, MxaStepPolicySpec ps,
+    double* obs, int32_t* flags, int k_steps) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  int env = blockIdx.x;
+  if (env >= n_envs) return;
+  char* e = base + (size_t)env * stride;
+  mxa::Eng<CFG, false, false, INSTR> g(e, lds, trace_cap, ctx);
+  g.load();
+  const MxaStepPolicy& pol = ps.pol;
+  const mxa_policy& p = pol.p;
+  const mxa_state_spec& sp = ps.spec;
+  for (int i = 0; i < k_steps; i++) {
+    const size_t row = (size_t)i * n_envs + env;
+    double a[3] = {0.0, 0.0, 0.0};
+    int64_t ai = -1;
+    if (!(pol.first_zero && i == 0)) {
+      auto R = g.rh();
+      const double o[2] = {R->obs[0], R->obs[1]};
+      float q[qwave::kRegs] = {0.f, 0.f, 0.f, 0.f};
+      for (int f = 0; f < sp.n_feat; f++) {
+        const float xf = state_feature(R->obs, sp, f);
+        if (g.lane == f) q[0] = xf;
+      }
+      qwave::forward(p.params, p.n_layers, p.dims, g.lane, q);
+      const int greedy = qwave::argmax(q, p.dims[p.n_layers]);
+      ai = qwave::select(greedy, p.test, p.enough, p.u, p.rnd, p.eps, row);
+      action_of(p.table + 3 * ai, o, p.q0, a);
+    }
+    if (g.lane == 0) {
+      pol.a[row] = ai;
+      for (int j = 0; j < 3; j++) pol.act[3 * row + j] = a[j];
+    }
+    if (g.status == ST_RUNNING) {
+      g.rl_place_orders(a);
+      g.end_step = 0;
+      g.run(max_pops);
+      if (g.status == ST_RUNNING) {  // after the loop: terminateRunner if the queue ran dry / past stop
+        u64 key;
+        u32 s;
+        if (g.q_peek(key, s) < 0 || g.cur > mxa::Eng<CFG>::PC.stop) g.status = ST_DONE;
+      }
+      if (g.status == ST_DONE) g.rp_terminate();
+    }
+    auto R = g.rh();
+    if (g.lane < 9) obs[9 * row + g.lane] = R->obs[g.lane];
+    u64 key;
+    u32 sq;
+    const bool pending = g.q_peek(key, sq) >= 0;  // all lanes: DPP reduction
+    // ABIDESEnv.step: done = not (queue non-empty and currentTime <= stopTime)
+    const int done = !(pending && g.cur <= mxa::Eng<CFG>::PC.stop) || g.status != ST_RUNNING;
+    const int hobs = mxa::U(R->has_obs);
+    if (g.lane == 0) flags[row] = done | (hobs ? 2 : 0) | (g.status == ST_ERROR ? 4 : 0);
+    if (pol.state != nullptr) g.rl_state_row(pol.state + (size_t)MXA_RL_STATE_WORDS * row);
+  }
+  g.save();
+  g.prof_flush();
+}
 #endif
 
 #ifdef MXA_API_TU  // (compiled once, in the C-ABI translation unit)

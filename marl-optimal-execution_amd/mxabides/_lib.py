@@ -78,6 +78,12 @@ class Policy(ctypes.Structure):  # mxa_policy: device pointers, host widths and 
                 ("eps", ctypes.c_void_p)]
 
 
+class StateSpec(ctypes.Structure):  # mxa_state_spec (include/mxa_state_spec.h): host fields, `grid` a device pointer
+    _fields_ = [("n_feat", ctypes.c_int32), ("col", ctypes.c_int32 * 8), ("mul", ctypes.c_double * 8),
+                ("div", ctypes.c_double * 8), ("add", ctypes.c_double * 8), ("grid", ctypes.c_void_p),
+                ("goff", ctypes.c_int32 * 9)]
+
+
 class AgentFinal(ctypes.Structure):  # mxa_agent_final
     _fields_ = [("final_fundamental", ctypes.c_int64), ("valuation_int", ctypes.c_int64), ("valuation", ctypes.c_double),
                 ("kind", ctypes.c_int32), ("err", ctypes.c_int32)]
@@ -175,6 +181,11 @@ BARS_BINDINGS = {
 VARIATE_BINDINGS = {
     "mxa_variate_probe": ([_I32, _U32, _P, _I32, _I32, _P, _P], _I32),
 }
+# the export of include/mxa_policy_features.h (the closed-loop step with a state of N features; a part of mxa.h's C-ABI too)
+POLICY_FEATURES_BINDINGS = {
+    "mxa_step_policy_spec": ([_P, _I32, _I32, ctypes.POINTER(Policy), ctypes.POINTER(StateSpec), _P, _P, _P, _P, _P],
+                             _I32),
+}
 COUNTER_WORDS = 34  # include/mxa.h MXA_COUNTER_WORDS
 INPLACE_WORDS = 12  # include/mxa.h MXA_INPLACE_WORDS
 RECORD_WORDS = 12  # include/mxa.h MXA_RECORD_WORDS
@@ -194,7 +205,7 @@ def load():
         raise MxaError("libmxa.so not built (%s); run __graft_entry__.build()" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in list(BINDINGS.items()) + list(SNAPSHOT_BINDINGS.items()) + list(DEPTH_BINDINGS.items()) \
-            + list(BARS_BINDINGS.items()) + list(VARIATE_BINDINGS.items()):
+            + list(BARS_BINDINGS.items()) + list(VARIATE_BINDINGS.items()) + list(POLICY_FEATURES_BINDINGS.items()):
         if hasattr(L, name):  # (MXA_LIB may name a variant build that lacks some)
             f = getattr(L, name)
             f.argtypes, f.restype = argtypes, restype

@@ -10,7 +10,11 @@ parallel envs on one device:
   features with the two grid axes, so the state is the two bin indices of time and quantity.
   Both features divide truly (remaining / total), on the CPU, in the PyTorch ops on the device
   and in libmxa_ddqn.so's kernels alike, so all three give np.digitize's bins of the reference's
-  own expressions (oracle/ddqn_ref.state_ref; a multiply by 1/quantity would not);
+  own expressions (oracle/ddqn_ref.state_ref; a multiply by 1/quantity would not). The four
+  features the reference's zip drops ("add market variables to observation TBD") can be had:
+  `ExecutionTask(features=[Feature(...), ...])` makes the state any 1..8 features of the
+  observation row, each binned on its own split points or passed through, in the PyTorch ops, the
+  per-period kernels and the policy inside the step kernel alike (include/mxa_state_spec.h);
 * the Q-network NNModel_1 (util/model/QNets.py:7-27: Dense 32-64-128-128-64-32 ReLU, Dropout 0.1
   after layers 2-6, linear 24-way head; Keras defaults glorot_uniform / zero bias), EvalModel and
   TargetModel (QNets.py:54-60); NNModel_2 (:30-51) by name;
@@ -98,6 +102,60 @@ def create_uniform_grid(low, high, bins=(10, 10)):
 def discretize(sample, grid):
     """agent/execution/util.py:25-40: np.digitize per dimension (zip truncates to the grid)."""
     return list(int(np.digitize(s, g)) for s, g in zip(sample, grid))
+
+
+# the observation row's columns (dummy_rl:294-315 and ABIDESEnvMetrics; mxa_kernels.hip rl_observe)
+(OBS_TIME_REMAINING, OBS_QTY_REMAINING, OBS_LOG_RETURN, OBS_SPREAD, OBS_VOLUME_IMBALANCE, OBS_SMART_PRICE,
+ OBS_VOLATILITY, OBS_TRADE_DIRECTION, OBS_EFFECTIVE_SPREAD) = range(9)
+OBS_COLUMNS = 9
+MAX_FEATURES = 8  # include/mxa_state_spec.h MXA_STATE_MAX_FEATURES
+MAX_SPLIT_POINTS = 1 << 20  # MXA_STATE_MAX_POINTS, all features together
+
+
+class Feature:
+    """One element of the learner's state (include/mxa_state_spec.h): x = mul * (obs[col] / div) + add
+    with a true division, then its bin on the feature's split points (np.digitize), or x itself when
+    it has none (a continuous input).  The split points are either a uniform grid, `bins` bins over
+    [low, high] as create_uniform_grid makes them (bins - 1 interior points), or `splits`, given
+    explicitly and strictly increasing.  Everything is checked here, on the host."""
+
+    def __init__(self, col, low=None, high=None, bins=0, splits=None, mul=1.0, div=1.0, add=0.0):
+        if int(col) != col or not 0 <= int(col) < OBS_COLUMNS:
+            raise ValueError("Feature: col %r is not an observation column 0..%d" % (col, OBS_COLUMNS - 1))
+        self.col = int(col)
+        self.mul, self.div, self.add = float(mul), float(div), float(add)
+        if not math.isfinite(self.div) or self.div == 0.0:
+            raise ValueError("Feature: div must be finite and nonzero, not %r" % (div,))
+        if not math.isfinite(self.mul) or not math.isfinite(self.add):
+            raise ValueError("Feature: mul and add must be finite")
+        if splits is not None:
+            if bins or low is not None or high is not None:
+                raise ValueError("Feature: either splits or a uniform grid (low, high, bins), not both")
+            pts = np.array(splits, dtype=np.float64).reshape(-1)
+            if not np.isfinite(pts).all() or not (np.diff(pts) > 0).all():
+                raise ValueError("Feature: splits must be finite and strictly increasing")
+        elif bins:
+            if int(bins) != bins or bins < 1 or low is None or high is None or not float(low) < float(high) \
+                    or not (math.isfinite(low) and math.isfinite(high)):
+                raise ValueError("Feature: a uniform grid needs bins >= 1 and finite low < high")
+            pts = create_uniform_grid([float(low)], [float(high)], (int(bins),))[0]
+        else:
+            if low is not None or high is not None:
+                raise ValueError("Feature: low and high without bins")
+            pts = np.zeros(0)
+        self.splits = np.ascontiguousarray(pts, dtype=np.float64)
+
+    def __repr__(self):
+        return "Feature(col=%d, %d split points, mul=%r, div=%r, add=%r)" % (self.col, len(self.splits), self.mul,
+                                                                            self.div, self.add)
+
+
+def default_features(quantity=100000, n_horizon=27):
+    """ExecutionTask's own two-element state as features: 2 * (time / n_horizon) - 1 and
+    2 * (quantity left / quantity) - 1 on the 200-bin grids over [0, 1]; bit for bit the states of
+    ExecutionTask() (x * 2 + (-1.0) and x * 2 - 1.0 are one IEEE operation)"""
+    return [Feature(OBS_TIME_REMAINING, 0.0, 1.0, GRID_BINS[0], mul=2.0, div=float(int(n_horizon)), add=-1.0),
+            Feature(OBS_QTY_REMAINING, 0.0, 1.0, GRID_BINS[1], mul=2.0, div=float(quantity), add=-1.0)]
 
 
 class QNet(nn.Module):
@@ -254,6 +312,7 @@ class DDQNLearner:
         self.eval_model, self.eflat = self._flat(QNet(n_state, n_actions, model, dropout, cpu))
         self.target_model, self.tflat = self._flat(QNet(n_state, n_actions, model, dropout, cpu))
         self.n_actions = n_actions
+        self.n_state = int(n_state)
         # the layer widths, as mxa_qnet_* take them (a host array)
         widths = [n_state] + [lin.out_features for lin in self.eval_model.hidden] + [n_actions]
         self._qdims = (ctypes.c_int * len(widths))(*widths)
@@ -377,6 +436,7 @@ class DDQNLearner:
             out_a = torch.empty(n, dtype=torch.int64, device=self.device)
         obs_w, obs_p, tab_p, act_p, q0 = 2, None, None, None, 1.0
         if obs is not None:
+            _check_width(self, task)
             if out_act is None:
                 out_act = torch.empty((n, 3), dtype=torch.float64, device=self.device)
             table = task.table
@@ -402,13 +462,16 @@ class DDQNLearner:
         VecABIDESEnv.step_policy_device: the flat parameters and widths, `task`'s grid, action table,
         horizon and quantity, epsilon, and choose_action's draws u / rnd ([k, n] float64 / int64
         device tensors; None in test mode). The tensors it points to stay referenced by the returned
-        object, which the caller keeps until the launch is enqueued."""
+        object, which the caller keeps until the launch is enqueued.  For a task with features the
+        grid fields stay null (mxa_step_policy_spec does not read them): the state is `task.spec`,
+        which the caller passes to step_policy_device beside this object."""
         from . import _lib
         if not self.fused_act:
             raise RuntimeError("DDQNLearner.policy needs fused_act (the in-kernel Q-values carry its bits)")
-        g0, g1 = (g.contiguous() for g in task.grid)
+        _check_width(self, task)
         table = task.table.contiguous()
-        for name, t, dt in (("grid", g0, torch.float64), ("grid", g1, torch.float64), ("table", table, torch.float64)):
+        grids = () if task.spec is not None else tuple(g.contiguous() for g in task.grid)
+        for name, t, dt in tuple(("grid", g, torch.float64) for g in grids) + (("table", table, torch.float64),):
             if t.dtype != dt or t.device != self.eflat.device:
                 raise ValueError("policy: task.%s must be a %s tensor on the learner's device" % (name, dt))
         if table.dim() != 2 or table.shape[0] < self.n_actions or table.shape[1] != 3:
@@ -421,13 +484,15 @@ class DDQNLearner:
         p.params, p.n_layers = self.eflat.data_ptr(), len(self._qdims) - 1
         for i, w in enumerate(self._qdims):
             p.dims[i] = w
-        p.grid0, p.n0, p.grid1, p.n1 = g0.data_ptr(), g0.numel(), g1.data_ptr(), g1.numel()
+        if grids:
+            g0, g1 = grids
+            p.grid0, p.n0, p.grid1, p.n1 = g0.data_ptr(), g0.numel(), g1.data_ptr(), g1.numel()
         p.nh, p.q0, p.table = float(task.nh), float(task.q0), table.data_ptr()
         p.test, p.enough = int(bool(test)), int(bool(enough))
         p.u = None if test else u.data_ptr()
         p.rnd = None if test else rnd.data_ptr()
         p.eps = self._eps.data_ptr()
-        p.keep = (self.eflat, g0, g1, table, u, rnd, self._eps)
+        p.keep = (self.eflat, grids, task.spec, table, u, rnd, self._eps)
         return p
 
     def choose_action(self, s):
@@ -575,9 +640,17 @@ class ExecutionTask:
     and reward (ddqlearning_execution_agent.py:301-331, 364-407, 409-446).
 
     obs[0] = remaining horizon steps, obs[1] = remaining quantity (dummy_rl:294-315); the
-    horizon has `n_horizon` points; the parent order is `quantity` shares BUY."""
+    horizon has `n_horizon` points; the parent order is `quantity` shares BUY.
 
-    def __init__(self, quantity=100000, n_horizon=27, device="cuda"):
+    features (a list of 1..8 Feature): the state is those features of the observation row instead,
+    `n_state` wide, so the policy can see the market columns (OBS_SPREAD, OBS_VOLUME_IMBALANCE, ...).
+    `spec` is then the task's mxa_state_spec (_lib.StateSpec, its split points on `device`), which
+    the kernels take (include/mxa_ddqn_features.h, mxa_policy_features.h), and `state` the same in
+    PyTorch ops: the CPU and fused=False path, bit for bit the kernels'.  None: today's two-element
+    state on today's code path (`spec` is None, `n_state` 2); default_features() is that state as
+    a feature list."""
+
+    def __init__(self, quantity=100000, n_horizon=27, device="cuda", features=None):
         self.q0 = float(quantity)
         self.nh = int(n_horizon)
         self.child = int(self.q0 / (self.nh - 1))  # generate_schedule: int(quantity / (len - 1))
@@ -592,10 +665,45 @@ class ExecutionTask:
         # the scalar's reciprocal and lands one bin off np.digitize at 73 of the quantities 0..1e5
         self._nh = torch.tensor(float(self.nh), dtype=torch.float64, device=device)
         self._q0 = torch.tensor(self.q0, dtype=torch.float64, device=device)
+        self.features, self.spec, self.n_state = None, None, 2
+        if features is not None:
+            self._set_features(list(features), device)
+
+    def _set_features(self, features, device):
+        from . import _lib
+        if not 1 <= len(features) <= MAX_FEATURES or not all(isinstance(f, Feature) for f in features):
+            raise ValueError("ExecutionTask: features must be a list of 1..%d Feature" % MAX_FEATURES)
+        if sum(len(f.splits) for f in features) > MAX_SPLIT_POINTS:
+            raise ValueError("ExecutionTask: more than %d split points in all" % MAX_SPLIT_POINTS)
+        self.features, self.n_state = features, len(features)
+        # every feature's split points in one device array (the spec's `grid`); a feature's own are a view of it
+        self._points = torch.tensor(np.concatenate([f.splits for f in features]), dtype=torch.float64, device=device)
+        sp = _lib.StateSpec()
+        sp.n_feat, off = len(features), 0
+        self._fgrid, self._fdiv = [], []
+        for i, f in enumerate(features):
+            sp.col[i], sp.mul[i], sp.div[i], sp.add[i] = f.col, f.mul, f.div, f.add
+            sp.goff[i] = off
+            self._fgrid.append(self._points[off:off + len(f.splits)] if len(f.splits) else None)
+            # 0-dim device tensors, for the same reason as _nh and _q0: tensor / tensor divides truly
+            self._fdiv.append(torch.tensor(f.div, dtype=torch.float64, device=device))
+            off += len(f.splits)
+        for i in range(len(features), len(sp.goff)):
+            sp.goff[i] = off
+        sp.grid = self._points.data_ptr() if off else None
+        sp.keep = self._points  # the struct points into it
+        self.spec = sp
 
     def state(self, obs):
         """discretize([2*rem_t/len - 1, 2*rem_q/q0 - 1]) -> float [n, 2] bin indices; true
-        divisions, as the reference's numpy (:307-308; oracle/ddqn_ref.state_ref)."""
+        divisions, as the reference's numpy (:307-308; oracle/ddqn_ref.state_ref).  With features:
+        float [n, n_state], per feature mul * (obs[:, col] / div) + add, binned or cast."""
+        if self.features is not None:
+            cols = []
+            for f, g, d in zip(self.features, self._fgrid, self._fdiv):
+                x = f.mul * (obs[:, f.col] / d) + f.add
+                cols.append(x if g is None else torch.bucketize(x, g, right=True))
+            return torch.stack([c.to(torch.float32) for c in cols], 1)
         tr = 2 * (obs[:, 0] / self._nh) - 1
         qr = 2 * (obs[:, 1] / self._q0) - 1
         # np.digitize(x, increasing bins) == torch.bucketize(x, bins, right=True)
@@ -655,18 +763,55 @@ def lib():
     return _LIB
 
 
+_FEATURES_LIB = None
+
+
+def features_lib():
+    """libmxa_ddqn_features.so (include/mxa_ddqn_features.h) as a ctypes.CDLL with its exports'
+    argtypes set: the per-period kernels for a task with features (ExecutionTask(features=...)). A
+    library beside libmxa_ddqn.so, built with it (build_lib.build_ddqn); None when it is not built"""
+    global _FEATURES_LIB
+    if _FEATURES_LIB is None:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "libmxa_ddqn_features.so")
+        if not os.path.exists(path):
+            return None
+        from ._lib import StateSpec
+        L = ctypes.CDLL(path)
+        P, I, I64, D, SPEC = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.POINTER(StateSpec)
+        L.mxa_ddqn_state_spec.argtypes = [P, I, I, P, SPEC, P]
+        L.mxa_ddqn_period_spec.argtypes = [P, I, I, I, I] + [P] * 13 + [SPEC, D, D, P, P, P, P, I64, P, P]
+        _FEATURES_LIB = L
+    return _FEATURES_LIB
+
+
 period_lib = lib  # the name bench.py asks by
 qnet_lib = lib  # the Q-network exports' loader by its earlier name, for callers that predate lib()
 
 
 def _call(name, *args):
-    """the export `name` of lib() on the current torch stream; a hipError_t raises"""
-    rc = getattr(lib(), name)(torch.cuda.current_stream().cuda_stream, *args)
+    """the export `name` of lib(), or of features_lib() for the *_spec kernels, on the current torch
+    stream; a hipError_t raises, and so does a features library that is not built (no fall-back)"""
+    L = lib()
+    if name.endswith("_spec"):
+        L = features_lib()
+        if L is None:
+            raise RuntimeError("%s: libmxa_ddqn_features.so is not built (build_lib.build_ddqn)" % name)
+    rc = getattr(L, name)(torch.cuda.current_stream().cuda_stream, *args)
     if rc:
         raise RuntimeError("%s: hip error %d" % (name, rc))
 
 
+def _check_width(learner, task):
+    """a learner whose network is not as wide as the task's state is refused before any launch"""
+    if learner.n_state != task.n_state:
+        raise ValueError("DDQNLearner(n_state=%d) does not match the task's state of %d element(s)"
+                         % (learner.n_state, task.n_state))
+
+
 def _state_device(task, obs, out):
+    if task.spec is not None:
+        _call("mxa_ddqn_state_spec", obs.shape[0], obs.shape[1], obs.data_ptr(), ctypes.byref(task.spec), out.data_ptr())
+        return out
     _call("mxa_ddqn_state", obs.shape[0], obs.shape[1], obs.data_ptr(), task.grid[0].data_ptr(), task.grid[0].numel(),
           task.grid[1].data_ptr(), task.grid[1].numel(), float(task.nh), task.q0, out.data_ptr())
     return out
@@ -708,8 +853,17 @@ def period_kernel(task, m, train, obs, st, prev, arrival, flags, alive, s, a, en
     next alive mask and the update mask are written into the three buffers of `spare` and returned.
     The kernel refuses a training batch of more envs than the replay capacity."""
     s2, alive_next, live = spare
-    g0, g1 = task.grid
     n = obs.shape[0]
+    if task.spec is not None:  # include/mxa_ddqn_features.h: the rows of s, s2 and the ring are n_state wide
+        _call("mxa_ddqn_period_spec", n, obs.shape[1], st.shape[1], int(train), obs.data_ptr(), st.data_ptr(),
+              prev.data_ptr(), arrival.data_ptr(), flags.data_ptr(), alive.data_ptr(), alive_next.data_ptr(),
+              live.data_ptr(), s.data_ptr(), a.data_ptr(), s2.data_ptr(), r_row.data_ptr(), env_steps.data_ptr(),
+              ctypes.byref(task.spec), task.q0, 1e4 / task.q0, m.s.data_ptr(), m.s2.data_ptr(), m.a.data_ptr(),
+              m.r.data_ptr(), m.cap, m.n_dev.data_ptr(), stored.data_ptr())
+        if train:
+            m.n_ub += n
+        return spare
+    g0, g1 = task.grid
     _call("mxa_ddqn_period", n, obs.shape[1], st.shape[1], int(train), obs.data_ptr(), st.data_ptr(), prev.data_ptr(),
           arrival.data_ptr(), flags.data_ptr(), alive.data_ptr(), alive_next.data_ptr(), live.data_ptr(), s.data_ptr(),
           a.data_ptr(), s2.data_ptr(), r_row.data_ptr(), env_steps.data_ptr(), g0.data_ptr(), g0.numel(), g1.data_ptr(),
@@ -770,7 +924,7 @@ def _run_rollout(env, learner, task, train_every, updates_per_train, record, tim
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
         env.step_policy_device(k, pol, obs[r0].data_ptr(), flags[r0].data_ptr(), a_idx[r0].data_ptr(),
-                               act[r0].data_ptr(), st[r0].data_ptr(), first_zero=first_zero)
+                               act[r0].data_ptr(), st[r0].data_ptr(), first_zero=first_zero, spec=task.spec)
         if timing is not None:
             e1.record()
             timing.append((e0, e1))
@@ -783,7 +937,7 @@ def _run_rollout(env, learner, task, train_every, updates_per_train, record, tim
                 ctx["arrival"] = torch.where(lob_ok, (st[0][:, 3] + st[0][:, 4]) / 2,
                                              torch.ones_like(st[0][:, 3])).contiguous()
                 ctx["env_steps"] = ctx["alive"].to(torch.int64)
-                ctx["s"] = _state_device(task, obs[0], torch.empty((n, 2), dtype=torch.float32, device=dev))
+                ctx["s"] = _state_device(task, obs[0], torch.empty((n, task.n_state), dtype=torch.float32, device=dev))
                 ctx["spare"] = (torch.empty_like(ctx["s"]), torch.zeros_like(ctx["alive"]),
                                 torch.zeros((), dtype=torch.bool, device=dev))
                 continue
@@ -843,10 +997,12 @@ def run_episode(env, learner, task, seeds=None, train_every=5, updates_per_train
     default) turns it on only where the environment has MXA_DDQN_ROLLOUT=1 and all of that holds.
     Until the replay holds a batch (choose_action's `enough`), a launch runs one period."""
     from .gym import OBS_SIZE, RL_STATE_WORDS
+    _check_width(learner, task)
     kernel = fused is not False and learner.device.type == "cuda" and lib() is not None
     if fused and not kernel:
         raise RuntimeError("run_episode(fused=True): libmxa_ddqn.so is not built (build_lib.build_ddqn)")
-    can_roll = kernel and learner.fused_act and hasattr(env.L, "mxa_step_policy")
+    can_roll = kernel and learner.fused_act and hasattr(env.L, "mxa_step_policy" if task.spec is None
+                                                        else "mxa_step_policy_spec")
     if rollout and not can_roll:
         raise RuntimeError("run_episode(rollout=True) needs the kernel path (fused not False), a CUDA learner with "
                            "fused_act, libmxa_ddqn.so and a libmxa.so with mxa_step_policy")
@@ -875,7 +1031,7 @@ def run_episode(env, learner, task, seeds=None, train_every=5, updates_per_train
     stored = torch.zeros((), dtype=torch.int64, device=dev)
     env_steps = alive.to(torch.int64)  # per env: ABIDESEnv.step calls taken while alive (the first one included)
     if kernel:  # the kernels fill preallocated buffers: the action vectors, and (s2, alive_next, live)
-        s = _state_device(task, obs, torch.empty((n, 2), dtype=torch.float32, device=dev))
+        s = _state_device(task, obs, torch.empty((n, task.n_state), dtype=torch.float32, device=dev))
         out = torch.empty((n, 3), dtype=torch.float64, device=dev)
         spare = (torch.empty_like(s), torch.zeros_like(alive), torch.zeros((), dtype=torch.bool, device=dev))
     else:

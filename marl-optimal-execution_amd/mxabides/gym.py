@@ -108,12 +108,22 @@ class VecABIDESEnv(Handle):
         self._check(self.L.mxa_step_many(self._h, int(k), ctypes.c_void_p(d_actions), ctypes.c_void_p(d_obs),
                                          ctypes.c_void_p(d_flags)), "mxa_step_many")
 
-    def step_policy_device(self, k, policy, d_obs, d_flags, d_a, d_act, d_state=None, first_zero=False):
+    def step_policy_device(self, k, policy, d_obs, d_flags, d_a, d_act, d_state=None, first_zero=False, spec=None):
         """k periods in one asynchronous launch with the epsilon-greedy Q-network policy evaluated in
         the step kernel (include/mxa.h mxa_step_policy): `policy` is an _lib.Policy (DDQNLearner.policy),
         the device buffers are obs [k][n][9], flags [k][n], a [k][n] int64, act [k][n][3] and, when
         given, state [k][n][RL_STATE_WORDS]; period i equals the i-th of k rounds of mxa_ddqn_state,
-        mxa_qnet_act, step_device and write_rl_state. first_zero: step 0 places (0, 0, 0)"""
+        mxa_qnet_act, step_device and write_rl_state. first_zero: step 0 places (0, 0, 0).
+        spec (an _lib.StateSpec, ExecutionTask(features=...).spec): the network's input row is the
+        spec's state of the observation, policy.dims[0] wide (include/mxa_policy_features.h
+        mxa_step_policy_spec; the sequence starts with mxa_ddqn_state_spec)"""
+        if spec is not None:
+            self._check(self.L.mxa_step_policy_spec(self._h, int(k), 1 if first_zero else 0, ctypes.byref(policy),
+                                                    ctypes.byref(spec), ctypes.c_void_p(d_obs), ctypes.c_void_p(d_flags),
+                                                    ctypes.c_void_p(d_a), ctypes.c_void_p(d_act),
+                                                    ctypes.c_void_p(d_state) if d_state else None),
+                        "mxa_step_policy_spec")
+            return
         self._check(self.L.mxa_step_policy(self._h, int(k), 1 if first_zero else 0, ctypes.byref(policy),
                                            ctypes.c_void_p(d_obs), ctypes.c_void_p(d_flags), ctypes.c_void_p(d_a),
                                            ctypes.c_void_p(d_act), ctypes.c_void_p(d_state) if d_state else None),
