@@ -839,9 +839,69 @@ constexpr Shape custom_shape(const mxa_config& c) {
   return S;
 }
 
+// a double that is neither NaN nor an infinity (constexpr: no <cmath> call)
+constexpr bool custom_finite(double x) { return x - x == 0; }
+// the first double field of the composition that is not finite, or 0.  No reference expression
+// survives one: every such value ends in int(round(nan)) (ValueError) or an event time that no
+// Timedelta holds, and the device would compile it into the kernels as an immediate
+constexpr const char* custom_nonfinite(const mxa_config& c) {
+  for (int g = 0; g < MXA_CONFIG_ZI_GROUPS; g++)
+    if (!custom_finite(c.zi_eta[g])) return "zi_eta is not finite";
+#define MXA_FIN(f) \
+  if (!custom_finite(c.f)) return #f " is not finite"
+  MXA_FIN(zi_sigma_n);
+  MXA_FIN(zi_r_bar);
+  MXA_FIN(zi_kappa);
+  MXA_FIN(zi_sigma_s);
+  MXA_FIN(zi_sigma_pv);
+  MXA_FIN(zi_lambda_a);
+  MXA_FIN(r_bar);
+  MXA_FIN(kappa);
+  MXA_FIN(fund_vol);
+  MXA_FIN(megashock_lambda_a);
+  MXA_FIN(megashock_mean);
+  MXA_FIN(megashock_var);
+  MXA_FIN(value_sigma_n);
+  MXA_FIN(value_r_bar);
+  MXA_FIN(value_kappa);
+  MXA_FIN(value_sigma_s);
+  MXA_FIN(value_lambda_a);
+  MXA_FIN(mm.mm_pov);
+  MXA_FIN(lat_low);
+  MXA_FIN(lat_high);
+#undef MXA_FIN
+  return nullptr;
+}
+// the Bayesian estimate's parameters of the agents that read them (ValueAgent.py:153-201 for
+// rmsc03 and value_noise, ZeroIntelligenceAgent.py:215-263 for the sparse_zi bases; `zi` picks the
+// message), or 0
+constexpr const char* custom_estimate_check(bool zi, double r_bar, double kappa, double sigma_n, double sigma_s) {
+  // Where the reference raises: kappa = 0 and kappa = 2, `(1 - (1 - kappa) ** (2 * delta)) /
+  // (1 - (1 - kappa) ** 2)` is ZeroDivisionError (ValueAgent.py:172, ZeroIntelligenceAgent.py:234);
+  // below 0 the weight (1 - kappa) ** delta over a session's deltas in ns is OverflowError for all
+  // but |kappa| < ~1e-9.  The rest of the refusal is the model's domain, not a reference error: at
+  // tiny negative kappa, in (1, 2) and above 2 the reference runs (a negative base to an integral
+  // power), but (0, 1] is the only range in which 1 - kappa is a mean-reversion weight
+  if (!(kappa > 0 && kappa <= 1)) return zi ? "zi_kappa must lie in (0, 1]" : "value_kappa must lie in (0, 1]";
+  // sigma_n = 0: `(sigma_n * sigma_t) / (sigma_n + sigma_t)` with sigma_t starting at 0 is
+  // ZeroDivisionError (ValueAgent.py:180, ZeroIntelligenceAgent.py:242); below 0 observePrice's
+  // sqrt(sigma_n) is ValueError (SparseMeanRevertingOracle.py:221)
+  if (!(sigma_n > 0)) return zi ? "zi_sigma_n must be > 0" : "value_sigma_n must be > 0";
+  // a variance: below 0 the weights sigma_n / (sigma_n + sigma_tprime) leave [0, 1] and their
+  // denominator can reach 0 (ZeroDivisionError at ValueAgent.py:177); the reference raises at no
+  // other value, this one is refused as outside the model
+  if (!(sigma_s >= 0)) return zi ? "zi_sigma_s must be >= 0" : "value_sigma_s must be >= 0";
+  // the agent's first estimate is r_bar itself: past int32 the device's words cannot hold it.  From
+  // MXA_PRICE_MAX + 1 (2^30) to there the composition builds and its first such order stops the
+  // env with ERR_ORDER_PRICE (include/mxa.h), as any later price outside the range does
+  if (!(r_bar >= 0 && r_bar < 2147483648.0)) return zi ? "zi_r_bar must lie in [0, 2^31)" : "value_r_bar must lie in [0, 2^31)";
+  return nullptr;
+}
+
 // 0, or why the composition cannot be built (mxa_config_compile / mxa_create_config: MXA_EINVAL)
 constexpr const char* custom_check(const mxa_config& c) {
   if (!custom_base_ok(c.base)) return "base must be MXA_RMSC03, MXA_VALUE_NOISE, MXA_SPARSE_ZI_100 or MXA_SPARSE_ZI_1000";
+  if (const char* why = custom_nonfinite(c)) return why;
   if (c.n_noise < 0 || c.n_value < 0 || c.n_mm < 0 || c.n_momentum < 0 || c.n_zi_groups < 0) return "negative count";
   if (c.n_zi_groups > MXA_CONFIG_ZI_GROUPS) return "more than MXA_CONFIG_ZI_GROUPS ZI groups";
   for (int g = 0; g < c.n_zi_groups; g++)
@@ -851,7 +911,8 @@ constexpr const char* custom_check(const mxa_config& c) {
     if (c.n_noise || c.n_value || c.n_mm || c.n_momentum) return "sparse_zi bases hold ZI agents only";
     if (c.n_zi_groups < 1) return "sparse_zi bases need a ZI strategy table";
     if (c.zi_q_max < 1 || c.zi_q_max > 10) return "zi_q_max in 1..10";
-    if (!(c.zi_sigma_pv >= 0) || !(c.zi_lambda_a > 0) || !(c.zi_sigma_n >= 0)) return "ZI parameters";
+    if (!(c.zi_sigma_pv >= 0) || !(c.zi_lambda_a > 0)) return "ZI parameters";
+    if (const char* why = custom_estimate_check(true, c.zi_r_bar, c.zi_kappa, c.zi_sigma_n, c.zi_sigma_s)) return why;
   } else {
     if (c.n_zi_groups) return "ZI groups belong to the sparse_zi bases";
     if (c.base == MXA_CFG_VALUE_NOISE && (c.n_mm || c.n_momentum)) return "value_noise holds noise and value agents";
@@ -861,7 +922,8 @@ constexpr const char* custom_check(const mxa_config& c) {
       return "market maker options (num_ticks <= 60)";
     if (c.n_momentum && (c.mom_min_size < 0 || c.mom_max_size <= c.mom_min_size || c.mom_wake_up_freq_ns <= 0))
       return "momentum options: 0 <= min_size < max_size, wake_up_freq > 0";
-    if (!(c.value_lambda_a > 0) || !(c.value_sigma_n >= 0)) return "value agent parameters";
+    if (!(c.value_lambda_a > 0)) return "value agent parameters";
+    if (const char* why = custom_estimate_check(false, c.value_r_bar, c.value_kappa, c.value_sigma_n, c.value_sigma_s)) return why;
   }
   const int n = custom_n_agents(c);
   if (n < 2 || n > MXA_MAX_AGENTS) return "2 to 8191 agents";
@@ -870,6 +932,13 @@ constexpr const char* custom_check(const mxa_config& c) {
     return "session: 0 <= mkt_open < mkt_close, 0 <= kernel_start <= kernel_stop < 2^47 ns";
   if (c.base == MXA_CFG_RMSC03 && c.noise_wake_close_ns < c.noise_wake_open_ns) return "noise wake window";
   if (!(c.megashock_lambda_a > 0) || !(c.megashock_var >= 0) || !(c.fund_vol >= 0)) return "oracle parameters";
+  // kappa = 0: `(theta ** 2) / (2 * gamma)` is ZeroDivisionError (SparseMeanRevertingOracle.py:106);
+  // below 0 the process leaves its mean exponentially in ns and the values leave every word
+  if (!(c.kappa > 0)) return "kappa must be > 0";
+  // the oracle's mean is the exchange's opening price and the first f_log value
+  // (SparseMeanRevertingOracle.py:62-63): int32 words on the device.  The reference's max(0, v)
+  // (:113) keeps every later value at or above 0, so a mean below 0 is outside the model
+  if (!(c.r_bar >= 0 && c.r_bar < 2147483648.0)) return "r_bar must lie in [0, 2^31)";
   if (c.default_computation_delay_ns < 0 || c.starting_cash < 0) return "delay / cash";
   if (!custom_zi(c.base) && c.base != MXA_CFG_VALUE_NOISE && (c.lat_low != 0 || c.lat_high != 0)) {
     // rmsc03's latency is zeros (no draw); the field is not used there

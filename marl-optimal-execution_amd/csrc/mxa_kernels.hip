@@ -1064,6 +1064,12 @@ struct Eng {
   // book-update log of this env: a kernel variant of its own (LOG), so the event loop of the
   // plain kernels carries none of it
   static constexpr bool BLOG = LOG;
+  // a runtime composition's limit prices lie in 1 .. MXA_PRICE_MAX (include/mxa.h): its caller's
+  // r_bar and variances are immediates here, and the book-update record's classes (a cancel is
+  // -price, a modify bit 30 of it) and the reference's `if bid and ask` leave no other price a
+  // meaning.  The built-in configurations' prices sit five decimal orders inside and keep their code
+  static constexpr bool PRICE_CHK = mxa_cfg::is_custom(CFG);
+  static DEV bool price_ok(i64 p) { return p >= 1 && p <= (i64)MXA_PRICE_MAX; }
   BlRec* blog;
   i32 blog_cap;
 #ifdef MXA_PROF
@@ -1979,6 +1985,12 @@ struct Eng {
     i64 vi = py_round(v);
     h.o_pt = ts;
     h.o_pv = (double)vi;
+    if constexpr (BLOG && PRICE_CHK) {  // the record's qty word is 32-bit (vi >= 0: the clamp above)
+      if (MXA_UNLIKELY(vi > INT32_MAX)) {
+        fail(ERR_ORDER_PRICE);
+        return (double)vi;
+      }
+    }
     if constexpr (BLOG) bl_put(ts, BL_FUNDAMENTAL, (i32)vi);  // f_log (SMRO:122)
     return (double)vi;
   }
@@ -2701,6 +2713,12 @@ struct Eng {
   // quantity) or the caller's order_id (SpreadBasedMarketMakerAgent)
   DEV void place_limit_oid(i64 qty, int is_buy, i64 price, i64 oid) {
     if (qty > 0) {
+      if constexpr (PRICE_CHK) {  // stop loudly: never a wrapped or re-classed price in an order word
+        if (MXA_UNLIKELY(!price_ok(price))) {
+          fail(ERR_ORDER_PRICE);
+          return;
+        }
+      }
       i32 n = rgi(AF_NORD);
       if (MXA_UNLIKELY(n >= PC.L.open_cap)) {
         fail(ERR_OPEN_FULL);
@@ -3147,7 +3165,7 @@ struct Eng {
       // both insides known: bid / ask are the best prices of the book as it stands (the reply was
       // built from it in this pop), so the exchange's match test is a compare.  A one-sided book
       // takes the queued path
-      if (hb && ha) {
+      if (hb && ha && (!PRICE_CHK || price_ok(p))) {  // (a price outside the range: place_limit stops the env)
         const i32 pi = (i32)p;
         return value_order(rgi(AF_SIZE), buy, pi, buy ? pi < ask : pi > bid, room);
       }
@@ -3245,6 +3263,13 @@ struct Eng {
       if constexpr (PC.mm_rt) {  // the order words are 32-bit: stop loudly, never wrap a ladder price
         const i64 t = mm_ticks();
         if (MXA_UNLIKELY(mid + mm_window() + t > INT32_MAX || mid - 1 - t < INT32_MIN)) {
+          fail(ERR_ORDER_PRICE);
+          return;
+        }
+      }
+      if constexpr (PRICE_CHK) {  // a composition's ladder, lowest bid to highest ask, before it cancels or places
+        const i64 t = mm_ticks();
+        if (MXA_UNLIKELY(!price_ok(mid - 1 - t) || !price_ok(mid + mm_window() + t))) {
           fail(ERR_ORDER_PRICE);
           return;
         }
@@ -5456,7 +5481,8 @@ struct Eng {
       o.price = me ? d : o.price;
     }
     bool ok = nc <= 64 && (nc == 0 || first >= 2) && sz > 0 && nord + CNL <= PC.L.open_cap && nc + CNL <= PC.L.open_cap &&
-              budget >= 5 + 2 * (nc + CNL) && qcount + nc + CNL + 1 <= QCAP && lb >= 0 && la + PC.mm_ticks <= INT32_MAX;
+              budget >= 5 + 2 * (nc + CNL) && qcount + nc + CNL + 1 <= QCAP && lb >= 0 && la + PC.mm_ticks <= INT32_MAX &&
+              (!PRICE_CHK || (price_ok(lb) && price_ok(la + PC.mm_ticks)));  // (mm_requote stops the env)
     int hit[SO];
     if (ok) ok = ex_cancel_find(mem, o.oid, o.price, o.is_buy, hit);
     if (ok) {

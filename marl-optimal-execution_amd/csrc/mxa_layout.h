@@ -101,7 +101,9 @@ enum {
   ERR_RP_QUOTE_SIZE = 30,
   // a limit price beyond the device's 32-bit order words (POVMarketMakerAgent with per-env options:
   // mid + --mm-window-size + --mm-num-ticks past INT32_MAX); the reference's Python int has no
-  // bound, so the env stops at that requote
+  // bound, so the env stops at that requote.  In a runtime composition: the first limit order of
+  // any agent class outside 1 .. MXA_PRICE_MAX (include/mxa.h), or, with the book-update log on, a
+  // fundamental value beyond the f_log record's int32 quantity word
   ERR_ORDER_PRICE = 31
 };
 

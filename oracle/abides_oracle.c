@@ -559,6 +559,10 @@ static double o_compute(ora_env* e, int64_t ts, double v_adj, int64_t pt, double
     int64_t vi = py_round(v);
     e->o_pt = ts;
     e->o_pv = (double)vi;
+    if (e->book_log && e->price_words && e->has_cfg && vi > INT32_MAX) { /* the f_log record's 32-bit quantity word */
+        fail(e, ORA_ERR_ORDER_PRICE, "oracle fundamental value beyond the f_log record's 32-bit word (ora_set_price_words)");
+        return (double)vi;
+    }
     if (e->book_log) blr_push(e, ts, BL_FUNDAMENTAL, vi);
     return (double)vi;
 }
@@ -1275,10 +1279,34 @@ static void get_tv(ora_env* e, agent_t* a, int64_t lookback) {
     m.lookback = lookback;
     ta_send_ex(e, a, &m);
 }
+/* ora_set_price_words on a composition (ora_create_config): the device's price range of a runtime
+ * composition, 1 .. ORA_PRICE_MAX (include/mxa.h MXA_PRICE_MAX) */
+static int price_words_cfg(const ora_env* e) { return e->price_words && e->has_cfg; }
+static int price_ok(int64_t p) { return p >= 1 && p <= ORA_PRICE_MAX; }
+static const char* agent_class(const agent_t* a) {
+    switch (a->type) {
+    case AG_VALUE: return "ValueAgent";
+    case AG_NOISE: return "NoiseAgent";
+    case AG_ZI: return "ZeroIntelligenceAgent";
+    case AG_MOMENTUM: return "MomentumAgent";
+    case AG_POVMM: return "POVMarketMakerAgent";
+    default: return "agent";
+    }
+}
+static void fail_price(ora_env* e, const agent_t* a, const char* what, int64_t price) {
+    char b[160];
+    snprintf(b, sizeof b, "%s %s %lld outside the device's 1 .. 2^30 - 1 (ora_set_price_words)", agent_class(a), what,
+             (long long)price);
+    fail(e, ORA_ERR_ORDER_PRICE, b);
+}
 /* placeLimitOrder (TradingAgent.py:309-349) */
 static void place_limit(ora_env* e, agent_t* a, int64_t qty, int is_buy, int64_t price) {
     int64_t oid = next_order_id(e);
     if (qty > 0) {
+        if (price_words_cfg(e) && !price_ok(price)) { /* the id is consumed, nothing is sent, the handler runs on */
+            fail_price(e, a, "limit price", price);
+            return;
+        }
         if (e->cap_open > 0 && a->nord >= e->cap_open) { /* one open order more than the device's list holds */
             fail(e, ORA_ERR_OPEN_FULL, "open-order list over the device's capacity (ora_set_open_capacity)");
             return;
@@ -1672,6 +1700,10 @@ static void mm_receive(ora_env* e, agent_t* a, const msg_t* m) {
         int64_t lb = hb - a->num_ticks, ha = la + a->num_ticks;
         if (e->price_words && (ha > INT32_MAX || lb < INT32_MIN)) { /* a ladder price the device cannot carry */
             fail(e, ORA_ERR_ORDER_PRICE, "market-maker ladder price beyond the device's 32-bit words (ora_set_price_words)");
+            return;
+        }
+        if (price_words_cfg(e) && (!price_ok(lb) || !price_ok(ha))) { /* a composition's ladder, before it cancels or places */
+            fail_price(e, a, "ladder price", price_ok(lb) ? ha : lb);
             return;
         }
         cancel_all(e, a);
@@ -3409,10 +3441,57 @@ static int build_config(ora_env* e, uint32_t seed, const ora_config* c) {
 /* kernelInitializing / kernelStarting of a built env (every creation path) */
 static int create_finish(ora_env* e, int rc, ora_env** out);
 
+/* The parameter refusals of the device's custom_check (csrc/mxa_config.h), with its messages: a
+ * value at which the reference raises (ValueAgent.py:153-201, ZeroIntelligenceAgent.py:215-263,
+ * SparseMeanRevertingOracle.py:88-125; the reasons stand beside the device's checks) or one the
+ * device cannot carry.  NULL: none applies */
+static const char* estimate_check(int zi, double r_bar, double kappa, double sigma_n, double sigma_s) {
+    if (!(kappa > 0 && kappa <= 1)) return zi ? "zi_kappa must lie in (0, 1]" : "value_kappa must lie in (0, 1]";
+    if (!(sigma_n > 0)) return zi ? "zi_sigma_n must be > 0" : "value_sigma_n must be > 0";
+    if (!(sigma_s >= 0)) return zi ? "zi_sigma_s must be >= 0" : "value_sigma_s must be >= 0";
+    if (!(r_bar >= 0 && r_bar < 2147483648.0)) return zi ? "zi_r_bar must lie in [0, 2^31)" : "value_r_bar must lie in [0, 2^31)";
+    return NULL;
+}
+const char* ora_config_check(const ora_config* c) {
+    for (int g = 0; g < ORA_CONFIG_ZI_GROUPS; g++)
+        if (!isfinite(c->zi_eta[g])) return "zi_eta is not finite";
+#define ORA_FIN(f) \
+    if (!isfinite(c->f)) return #f " is not finite"
+    ORA_FIN(zi_sigma_n);
+    ORA_FIN(zi_r_bar);
+    ORA_FIN(zi_kappa);
+    ORA_FIN(zi_sigma_s);
+    ORA_FIN(zi_sigma_pv);
+    ORA_FIN(zi_lambda_a);
+    ORA_FIN(r_bar);
+    ORA_FIN(kappa);
+    ORA_FIN(fund_vol);
+    ORA_FIN(megashock_lambda_a);
+    ORA_FIN(megashock_mean);
+    ORA_FIN(megashock_var);
+    ORA_FIN(value_sigma_n);
+    ORA_FIN(value_r_bar);
+    ORA_FIN(value_kappa);
+    ORA_FIN(value_sigma_s);
+    ORA_FIN(value_lambda_a);
+    ORA_FIN(mm.mm_pov);
+    ORA_FIN(lat_low);
+    ORA_FIN(lat_high);
+#undef ORA_FIN
+    const char* why = c->base == 1 || c->base == 2
+                          ? estimate_check(1, c->zi_r_bar, c->zi_kappa, c->zi_sigma_n, c->zi_sigma_s)
+                          : estimate_check(0, c->value_r_bar, c->value_kappa, c->value_sigma_n, c->value_sigma_s);
+    if (why) return why;
+    if (!(c->kappa > 0)) return "kappa must be > 0";
+    if (!(c->r_bar >= 0 && c->r_bar < 2147483648.0)) return "r_bar must lie in [0, 2^31)";
+    return NULL;
+}
+
 int ora_create_config(const ora_config* c, uint32_t seed, ora_env** out) {
     static const char* names[6] = {"rmsc03", "sparse_zi_100", "sparse_zi_1000", NULL, NULL, "value_noise"};
     if (!c || c->base < 0 || c->base > 5 || !names[c->base]) return -1;
     if (c->n_zi_groups < 0 || c->n_zi_groups > ORA_CONFIG_ZI_GROUPS || c->zi_q_max < 0 || c->zi_q_max > 10) return -1;
+    if (ora_config_check(c)) return -1;
     ora_env* e = (ora_env*)calloc(1, sizeof(ora_env));
     snprintf(e->config, sizeof e->config, "%s", names[c->base]);
     e->cfg_log_orders = c->log_orders ? 1 : 0;
@@ -3594,7 +3673,13 @@ void ora_set_capacities(ora_env* e, int64_t q, int64_t b) {
  * the order id is consumed, nothing is sent, the handler runs on.  0 leaves it unbounded. */
 void ora_set_open_capacity(ora_env* e, int64_t n) { e->cap_open = n; }
 /* the device's 32-bit limit-price words: the market maker's requote whose ladder would hold a
- * price outside int32 fails the env before it cancels or places anything */
+ * price outside int32 fails the env before it cancels or places anything.  On a composition
+ * (ora_create_config) the device's declared price range instead (include/mxa.h MXA_PRICE_MAX): the
+ * first placeLimitOrder with a quantity > 0 of any agent class at a price outside 1 .. 2^30 - 1
+ * fails the env (the order id is consumed, nothing is sent, the handler runs on), the market maker's
+ * ladder as a whole before it cancels or places, and, with the book log on, a fundamental value
+ * beyond the f_log record's 32-bit word; the message names the agent class.  Without this switch
+ * prices are unbounded int64, as the reference's are */
 void ora_set_price_words(ora_env* e, int on) { e->price_words = on; }
 void ora_stats(const ora_env* e, int64_t* out) {
     out[0] = e->st_max_heap;

@@ -89,6 +89,7 @@ void ora_set_open_capacity(ora_env* e, int64_t n);
  * would hold a price outside int32 (a huge --mm-window-size) fails the env in that pop, before it
  * cancels or places anything; the reference's Python int would carry the price. */
 #define ORA_ERR_ORDER_PRICE (-23)
+#define ORA_PRICE_MAX 1073741823 /* include/mxa.h MXA_PRICE_MAX */
 void ora_set_price_words(ora_env* e, int on);
 /* Kernel.summaryLog after ora_finish: (agent, type 0 STARTING_CASH / 1 FINAL_CASH_POSITION /
  * 2 ENDING_CASH / 3 FINAL_VALUATION, is-float, int value, float value); returns the row count */
@@ -166,6 +167,9 @@ typedef struct {
 } ora_config;
 int ora_config_defaults(const char* base, ora_config* out);
 int ora_create_config(const ora_config* c, uint32_t seed, ora_env** out);
+/* why ora_create_config refuses the composition's parameters (the device's refusals, with its
+ * messages: include/mxa.h mxa_config_compile), or NULL */
+const char* ora_config_check(const ora_config* c);
 /* ora_run_batch_err / _stats of one composition over n seeds */
 int ora_run_batch_config(const ora_config* c, const uint32_t* seeds, int n, int threads, int64_t max_pops,
                          int64_t* events_out, uint64_t* hash_out, int32_t* err_out, int64_t* stats_out,

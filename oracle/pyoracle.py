@@ -183,7 +183,10 @@ class OracleEnv:
             L.ora_create_config.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
             rc = L.ora_create_config(ctypes.byref(self._cfg), seed & 0xFFFFFFFF, ctypes.byref(self._h))
             if rc:
-                raise ValueError("oracle: bad composition")
+                L.ora_config_check.argtypes = [ctypes.c_void_p]
+                L.ora_config_check.restype = ctypes.c_char_p
+                why = L.ora_config_check(ctypes.byref(self._cfg))
+                raise ValueError("oracle: bad composition" + (": " + why.decode() if why else ""))
         elif mm is not None:
             if config != "rmsc03":
                 raise ValueError("market-maker options are config/rmsc03.py's")
@@ -217,7 +220,9 @@ class OracleEnv:
 
     def set_price_words(self, on=True):
         """the device's 32-bit limit-price words (ora_set_price_words): a market-maker ladder with a
-        price outside int32 fails the env with ERR_ORDER_PRICE; before run()"""
+        price outside int32 fails the env with ERR_ORDER_PRICE.  On a composition: the device's
+        price range 1 .. 2^30 - 1 (include/mxa.h MXA_PRICE_MAX) for every agent class's limit orders,
+        and int32 for the f_log values of the book log; the message names the class.  Before run()"""
         L = lib()
         L.ora_set_price_words.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.ora_set_price_words.restype = None
@@ -251,6 +256,10 @@ class OracleEnv:
     @property
     def events(self):
         return lib().ora_events(self._h)
+
+    @property
+    def current_time(self):
+        return lib().ora_current_time(self._h)
 
     def trace(self):
         n = lib().ora_trace_len(self._h)

@@ -59,6 +59,50 @@ COMPOSITIONS = {
                         [123456789, 7], True),
 }
 
+# The price and parameter edges (tests/composition_edges.py, include/mxa.h MXA_PRICE_MAX): rmsc03
+# with 20 noise, 10 value and 2 momentum agents over five minutes, value agents every 10 s
+_EDGE = {"n_noise": 20, "n_value": 10, "n_momentum": 2, "mkt_close_ns": (9 * 3600 + 35 * 60) * 10**9,
+         "kernel_stop_ns": (9 * 3600 + 36 * 60) * 10**9, "value_lambda_a": 1e-10}
+# one price only: no market maker, no momentum agents, a constant fundamental (fund_vol 0, the first
+# megashock 1e14 ns = 28 h away on average and of size 0 +- 0, so that the one in 280 seeds that
+# draws it inside the session changes no value) and an observation variance of 1e-6, so that every
+# estimate rounds to r_bar.  Buys and sells at that one price match on arrival: the book never has
+# two sides.  (A rarer megashock is no option: the reference formats the drawn interval with "{}ns"
+# and pd.Timedelta raises "invalid unit abbreviation: e" for a draw of 1e16 ns or more,
+# SparseMeanRevertingOracle.py:68; measured with megashock_lambda_a = 1e-16 on seed 1.)
+_FLAT = dict(_EDGE, n_mm=0, n_momentum=0, fund_vol=0.0, megashock_lambda_a=1e-14, megashock_mean=0.0,
+             megashock_var=0.0, value_sigma_n=1e-6)
+_PRICE_MAX = 2**30 - 1
+
+
+def _flat(r_bar, **kw):
+    return dict(_FLAT, r_bar=float(r_bar), value_r_bar=float(r_bar), **kw)
+
+
+COMPOSITIONS.update({
+    # a megashock every 0.1 s, of 100 +- 50 cents: about 3,300 fundamental values in five minutes
+    # against 300, several megashocks per observation, prices within 15 % of r_bar
+    "rmsc03_shocks": ("rmsc03", dict(_EDGE, megashock_lambda_a=1e-8, megashock_mean=100.0, megashock_var=2500.0),
+                      [1, 2], True),
+    # fundamental and estimates around 50 cents: the fundamental is clamped at 0 and the reference
+    # places orders at prices <= 0 and runs on (seed 15: 50 of its 321 orders, down to -35)
+    "rmsc03_low": ("rmsc03", dict(_EDGE, r_bar=50.0, value_r_bar=50.0, value_sigma_n=100.0), [15], True),
+    # just under 2^31: the reference's orders pass INT32_MAX (seed 26: 81 of its 323, up to 2147486369)
+    "rmsc03_high": ("rmsc03", dict(_EDGE, r_bar=2147483000.0, value_r_bar=2147483000.0, value_sigma_n=1e6),
+                    [26], True),
+    # every order at exactly MXA_PRICE_MAX / one cent above / at 1 / at 0
+    "rmsc03_top": ("rmsc03", _flat(_PRICE_MAX), [7], True),
+    "rmsc03_over": ("rmsc03", _flat(_PRICE_MAX + 1), [7], True),
+    "rmsc03_bottom": ("rmsc03", _flat(1), [7], True),
+    "rmsc03_zero": ("rmsc03", _flat(0), [7], True),
+    # the market maker under the top of the range.  With every order at one price the book never has
+    # two sides and the maker never quotes (measured on the oracle: 32 seeds of rmsc03_top with a
+    # market maker, no ladder), so this one has an observation variance of 4 around
+    # MXA_PRICE_MAX - 12: value orders reach MXA_PRICE_MAX - 3 and pass, the book has a spread, and
+    # the first ladder's asks (mid + 5 .. mid + 25) lie above the range
+    "rmsc03_top_mm": ("rmsc03", _flat(_PRICE_MAX - 12, n_mm=1, value_sigma_n=4.0), [1], True),
+})
+
 
 def full_composition(base, over):
     """the base script's composition (oracle/pyoracle.config_defaults, pinned against the device's

@@ -155,7 +155,8 @@ def exlog_digest(rows):
 # runtime compositions (tests/golden/gen_config_fixtures.py): (name, seed) of cfg_<name>_<seed>.*
 COMPOSITION_FIXTURES = [("rmsc03_n100_v20", 123456789), ("rmsc03_n100_v20", 7), ("rmsc03_alt", 123456789),
                         ("rmsc03_alt", 11), ("sparse_zi_alt", 123456789), ("sparse_zi_alt", 7),
-                        ("sparse_zi_matrix_200", 123456789), ("value_noise_alt", 123456789), ("value_noise_alt", 7)]
+                        ("sparse_zi_matrix_200", 123456789), ("value_noise_alt", 123456789), ("value_noise_alt", 7),
+                        ("rmsc03_shocks", 1), ("rmsc03_shocks", 2)]
 
 
 def load_composition(name, seed):
