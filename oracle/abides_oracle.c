@@ -1554,8 +1554,9 @@ static int zi_update_estimates(ora_env* e, agent_t* a, int64_t* v_out, int* buy_
     int64_t r_T = bayes_r_T(e, a, obs);
     q += a->q_max - 1;
     int64_t idx = buy ? q + 1 : q;
-    if (idx < 0) idx += 20; /* python negative index */
-    if (idx < 0 || idx >= 20) {
+    const int64_t nq = 2 * a->q_max; /* len(theta) (ZI.py:90-92) */
+    if (idx < 0) idx += nq; /* python negative index */
+    if (idx < 0 || idx >= nq) {
         fail(e, -6, "ZeroIntelligenceAgent theta index out of range (IndexError)");
         return 0;
     }

@@ -104,6 +104,33 @@ COMPOSITIONS.update({
 })
 
 
+# The reference's own crash in get_transacted_volume (tests/env_error_cases.py, env error 5
+# ERR_PANDAS_NO_TX): config/rmsc03.py's market maker beside one value agent and nobody else.  The
+# maker's first QUERY_TRANSACTED_VOLUME finds an order book history without a transaction and
+# OrderBook.get_transacted_volume reads a column of an empty DataFrame (AttributeError), after 19
+# events on seed 1; the fixture holds the trace up to the raise and the exception as stop_error.
+# Its clean neighbours: the maker alone (11 events: the history holds no order at all, so the
+# volume is 0 and nothing is read) and the maker beside two noise agents, which runs to the end.
+_MM_ONLY = {"n_noise": 0, "n_value": 0, "n_momentum": 0}
+COMPOSITIONS.update({
+    "rmsc03_mm_value1": ("rmsc03", dict(_MM_ONLY, n_value=1), [1], True),
+    "rmsc03_mm_only": ("rmsc03", dict(_MM_ONLY), [1], True),
+    "rmsc03_mm_noise2": ("rmsc03", dict(_MM_ONLY, n_noise=2), [1], True),
+    # Kernel.setWakeup's ValueError (env error 6 ERR_WAKEUP_PAST): the kernel starts 2 ns after the
+    # market opens, and an agent that learns the hours asks for its first wake-up at mkt_open + a
+    # draw from randint(0, 100).  A draw below 2 lies in the past: seeds 27 (6 events) and 13 (11
+    # events) of 1..64 on the oracle; seed 1 draws later wake-ups and runs the whole session
+    "rmsc03_late_start": ("rmsc03", dict(n_noise=2, n_value=2, n_mm=0, n_momentum=0,
+                                         kernel_start_ns=(9 * 3600 + 30 * 60) * 10**9 + 2), [27, 13, 1], True),
+    # ZeroIntelligenceAgent.updateEstimates' IndexError (env error 7 ERR_THETA_INDEX): q_max 1 is a
+    # theta list of two values, ten agents, and latencies up to 10 s.  An agent's cancel of its
+    # resting order travels while its next order executes, so both fill: 200 shares, q = 2 >
+    # q_max, theta[2] of two.  Seeds 2 (574 events) and 6 (406) of 1..32 on the oracle; seed 1 finishes
+    "sparse_zi_q1": ("sparse_zi_100", {"zi_table": [(10, 0, 250, 1)], "zi_q_max": 1, "lat_high": 1e10},
+                     [2, 6, 1], True),
+})
+
+
 def full_composition(base, over):
     """the base script's composition (oracle/pyoracle.config_defaults, pinned against the device's
     mxa_config_defaults by tests/test_composition.py) with the overrides, as a plain dict"""
