@@ -480,6 +480,7 @@ int mxa_read_book_log(mxa_handle* h, int32_t env, mxa_book_rec* out, int64_t cap
 #include "mxa_depth.h"
 #include "mxa_bars.h"
 #include "mxa_variates.h"
+#include "mxa_streams.h"
 #include "mxa_policy_features.h"
 
 /* parity probes: device numpy-legacy RNG (mode 0 u32, 1 double, 2 randint(a,b),

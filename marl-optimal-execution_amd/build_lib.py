@@ -41,7 +41,7 @@ CFG_FLAGS = {1: ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], 2: ["-fno-slp-vect
 
 
 def sources():
-    return [os.path.join(HERE, "csrc", d) for d in DEPS] + [os.path.join(ROOT, "include", h) for h in ("mxa.h", "mxa_snap.h", "mxa_depth.h", "mxa_bars.h", "mxa_variates.h", "mxa_policy_features.h", "mxa_state_spec.h")]
+    return [os.path.join(HERE, "csrc", d) for d in DEPS] + [os.path.join(ROOT, "include", h) for h in ("mxa.h", "mxa_snap.h", "mxa_depth.h", "mxa_bars.h", "mxa_variates.h", "mxa_streams.h", "mxa_policy_features.h", "mxa_state_spec.h")]
 
 
 def build_id(extra=()):

@@ -1400,6 +1400,23 @@ int mxa_variate_probe(int32_t device, uint32_t seed, const uint8_t* script, int3
   return hipMemcpy(state, d_state, sizeof(uint64_t) * 6 * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess ? MXA_OK : MXA_EHIP;
 }
 
+// include/mxa_streams.h
+int mxa_stream_head_probe(int32_t device, uint32_t seed, int32_t head_words, int32_t n, double* out_values,
+                          uint64_t* out_state) {
+  if (n <= 0 || !out_values || !out_state || head_words < 2 || head_words > MXA_STREAM_HEAD_WORDS) return MXA_EINVAL;
+  if (hipSetDevice(device) != hipSuccess) return MXA_EHIP;
+  DevBuf<double> d_out;
+  DevBuf<uint64_t> d_state;
+  DevBuf<uint32_t> d_s;
+  if (d_out.alloc((size_t)n) != hipSuccess || d_state.alloc(2 * (size_t)n) != hipSuccess || d_s.alloc(MXA_RNG_WORDS) != hipSuccess)
+    return MXA_ENOMEM;
+  if (hipMemset(d_s, 0, sizeof(uint32_t) * MXA_RNG_WORDS) != hipSuccess) return MXA_EHIP;
+  hipLaunchKernelGGL(mxa_stream_head_probe_kernel, dim3(1), dim3(64), 0, 0, seed, head_words, n, d_out.p, d_state.p, d_s.p);
+  if (hipGetLastError() != hipSuccess) return MXA_EHIP;
+  if (hipMemcpy(out_values, d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return MXA_EHIP;
+  return hipMemcpy(out_state, d_state, sizeof(uint64_t) * 2 * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess ? MXA_OK : MXA_EHIP;
+}
+
 int mxa_math_probe(int32_t device, int32_t mode, const double* x, const double* y, double* out, int64_t n) {
   if (n <= 0 || !x || !out) return MXA_EINVAL;
   if (hipSetDevice(device) != hipSuccess) return MXA_EHIP;

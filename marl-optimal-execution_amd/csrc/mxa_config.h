@@ -233,6 +233,43 @@ constexpr bool one_advance(int cfg) { return (((MXA_ONE_ADVANCE_MASK) >> cfg) & 
 #endif
 constexpr bool variate_o(int cfg) { return (((MXA_VARIATE_O_MASK) >> cfg) & 1) != 0 && !is_custom(cfg); }
 constexpr bool variate_agent(int cfg) { return (((MXA_VARIATE_AGENT_MASK) >> cfg) & 1) != 0 && !is_custom(cfg); }
+// Stream classes (DESIGN.md §4 "RNG streams", Appendix R.14): what the build kernel materialises of
+// an agent's own MT19937 stream (Agent.random_state), by the draws its class can make.
+//   full  the seeded state (block 0) and block 1, the run kernel's look-ahead
+//   head  block 1's first MXA_STREAM_HEAD_WORDS outputs and the state words they are made of
+//         (A[0..HEAD_WORDS] and A[397..397 + HEAD_WORDS)); a draw past them is ERR_RNG_OVERRUN
+//   none  the seed word alone (set_seed's key[0])
+// The table is derived from the agent_rs() sites of mxa_kernels.hip (tests/test_stream_classes.py
+// parses both: a new draw site of a head or none class fails there until its row is moved).
+// (MXA_STREAM_HEAD_WORDS and the MXA_STREAM_* class ids: mxa_layout.h)
+// ... bit = config id (a runtime composition follows its base): a unit outside the mask keeps every stream full
+#ifndef MXA_STREAM_CLASS_MASK
+#define MXA_STREAM_CLASS_MASK (~0)
+#endif
+constexpr int stream_class_of(int type) {
+  switch (type) {
+  case AG_NOISE:     // head: wake_frequency's randint(0, 100), once per episode (its orders draw from G)
+  case AG_MOMENTUM:  // head: the size draw of Builder::build; wake_frequency returns mom_wake before the draw
+    return MXA_STREAM_HEAD;
+  case AG_EXCHANGE:  // none: no agent_rs() site (dispatch never wakes it through wake_frequency)
+  case AG_POVMM:     // none: wake_frequency returns mm_wake()
+  case AG_SBMM:      // none: wake_frequency returns sb_wake
+  case AG_OBI:       // none: wake_frequency returns obi_wake
+  case AG_DUMMYRL:   // none: wake_frequency returns rl_h0 - mkt_open
+  case AG_REPLAY:    // none: wake_frequency returns the first tape time
+  case AG_TWAP:      // none: wake_frequency returns rl_h0 - mkt_open
+    return MXA_STREAM_NONE;
+  default:           // full: AG_VALUE, AG_ZI, AG_HBL, AG_MKTMAKER draw at every wake or placement
+    return MXA_STREAM_FULL;
+  }
+}
+constexpr int stream_class(int cfg, int type) {
+  return (((MXA_STREAM_CLASS_MASK) >> cfg) & 1) != 0 ? stream_class_of(type) : MXA_STREAM_FULL;
+}
+// the latency-model stream L (stream 3) is drawn only where lat_mode == 2 (Eng::KS): none elsewhere
+#ifndef MXA_STREAM_L_NONE
+#define MXA_STREAM_L_NONE 1
+#endif
 // a table: 64 slots of (ret, cache) doubles and the descriptor's two words in LDS; 64 slots of
 // (e, ret, cache, 0) in the env block, the descriptor in the agent's record (AF_VT_*)
 #define MXA_VT_O_BYTES ((2 * 64 + 2) * 8)

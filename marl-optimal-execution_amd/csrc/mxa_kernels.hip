@@ -321,6 +321,44 @@ DEV void mt_seed(u32* key, u32 s) {
   wfence();
 }
 
+// Head streams (mxa_config.h stream classes): the first hw (<= 64) outputs of block 1 are pure
+// phase 1 of the twist, B[i] = A[i + 397] ^ mt_mix(A[i], A[i + 1]), so they need the state words
+// A[0..hw] and A[397..397 + hw) and nothing else of the stream is ever stored.
+DEV bool mt_head_word(int i, int hw) { return i <= hw || (i >= MXA_MT_M && i < MXA_MT_M + hw); }
+// init_genrand for a head stream: mt_seed's recurrence, only the head's state words stored
+DEV void mt_seed_head(u32* key, u32 s, int hw) {
+  const int lane = laneid();
+  for (int i = 0; i < MXA_MT_M + hw; i++) {
+    if ((i & 63) == lane && mt_head_word(i, hw)) key[i] = s;
+    s = 1812433253u * (s ^ (s >> 30)) + (u32)i + 1u;
+  }
+  wfence();
+}
+// the heads of n (<= MT_HEAD_BATCH) streams in one memory round trip, lane = word: every stream's
+// three loads are issued before the first store (one in-order vmcnt covers both, as in mt_gen_pair)
+#define MT_HEAD_BATCH 8
+DEV void mt_gen_heads(u32* const* key, int n, int hw = MXA_STREAM_HEAD_WORDS) {
+  const int lane = laneid();
+  u32 a0[MT_HEAD_BATCH], a1[MT_HEAD_BATCH], a3[MT_HEAD_BATCH];
+#pragma unroll
+  for (int q = 0; q < MT_HEAD_BATCH; q++) {
+    const bool on = q < n && lane < hw;
+    const u32* A = key[q];  // (all MT_HEAD_BATCH entries are valid pointers; those from n on are not read)
+    a0[q] = on ? A[lane] : 0u;
+    a1[q] = on ? A[lane + 1] : 0u;
+    a3[q] = on ? A[lane + MXA_MT_M] : 0u;
+  }
+#pragma unroll
+  for (int q = 0; q < MT_HEAD_BATCH; q++)
+    if (q < n && lane < hw) key[q][MXA_MT_N + lane] = a3[q] ^ mt_mix(a0[q], a1[q]);
+  wfence();
+}
+// after a draw on a head stream: a position past the head read a word that was never materialised
+template <class R>
+DEV void rs_head_guard(R& r, int hw = MXA_STREAM_HEAD_WORDS) {
+  if (MXA_UNLIKELY(r.p > MXA_MT_N + hw)) r.hasg |= 2;
+}
+
 DEV u32 mt_temper(u32 y) {
   y ^= (y >> 11);
   y ^= (y << 7) & 0x9d2c5680u;
@@ -2866,6 +2904,7 @@ struct Eng {
     }
     ARS A = agent_rs();
     i64 v = rs_randint(A, 0, 100);
+    if (mxa_cfg::stream_class(CFG, type) == MXA_STREAM_HEAD) rs_head_guard(A);  // ERR_RNG_OVERRUN at rng_maint
     agent_rs_put(A);
     return v;
   }
@@ -6019,52 +6058,113 @@ struct Builder : Eng<CFG, true> {
     double mult = c + beta;
     return open + (i64)(mult * (double)(close - open));
   }
-  // expand every stream's init_genrand in parallel (lane = stream).  With room in the LDS queue
+  // expand the streams' init_genrand in parallel (lane = stream).  With room in the LDS queue
   // area (empty until the kernelStarting wakeups) each lane's 16-word runs go through an LDS tile
   // and leave as 64-byte runs of 4 streams per store instead of 64 scattered dwords.
+  // Only what the run reads is seeded (mxa_config.h stream classes): a none stream takes no lane, a
+  // head stream runs the recurrence and stores its head's state words alone, and the streams that
+  // are seeded fill the passes' lanes densely (rmsc03: 64 of its 67 streams after G, one pass).
   static constexpr bool SEED_TILE = E::LDS_Q >= 64 * 17 * 4;
+  static constexpr int HW = MXA_STREAM_HEAD_WORDS;
+  static_assert(HW <= 64 && HW + MXA_AGENT_LA < MXA_MT_N, "a head is one wave wide and inside block 1's look-ahead");
+  // O and K are full; L is drawn only by the latency model (Eng::KS); an agent's class is its type's,
+  // read from its record (every record but the exchange's, agent 0, is initialised before the seeding)
+  static constexpr bool L_NONE = (MXA_STREAM_L_NONE) && E::PC.lat_mode != 2 &&
+                                 mxa_cfg::stream_class(CFG, AG_EXCHANGE) == MXA_STREAM_NONE;
+  DEV int stream_cls(int s) {
+    if (s < 4) return s == 3 && L_NONE ? MXA_STREAM_NONE : MXA_STREAM_FULL;
+    if (s == 4) return mxa_cfg::stream_class(CFG, AG_EXCHANGE);
+    return mxa_cfg::stream_class(CFG, (int)((const u32*)this->agent_ptr(s - 4))[AF_TYPE]);
+  }
+  // one pass: the streams pend[0 .. cnt) (stream << 1 | head), lane = stream
+  DEV void seed_pass(LDSP const u32* pend, int cnt) {
+    const int lane = this->lane;
+    const u32 ent = lane < cnt ? pend[lane] : 1u;
+    const bool anyfull = bal(lane < cnt && !(ent & 1u)) != 0;
+    const int last = anyfull ? MXA_MT_N : MXA_MT_M + HW;  // a pass of heads ends with their last state word
+    if constexpr (SEED_TILE) {
+      LDSP u32* tile = (LDSP u32*)this->qk;  // [64 streams][17] (16 words + a bank-conflict pad)
+      u32 x = lane < cnt ? this->rng_key((int)(ent >> 1))[0] : 0u;
+      u32 se[16];  // the streams whose words this lane stores: 4 streams x 16 words per store
+#pragma unroll
+      for (int t = 0; t < 16; t++) {
+        const int st = 4 * t + (lane >> 4);
+        se[t] = st < cnt ? pend[st] : ~0u;
+      }
+      for (int i0 = 1; i0 < last; i0 += 16) {
+        // (a round no stream of the pass stores a word of only advances the recurrence)
+        const bool rnd = anyfull || i0 <= HW || (i0 + 15 >= MXA_MT_M && i0 < MXA_MT_M + HW);
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+          x = 1812433253u * (x ^ (x >> 30)) + (u32)(i0 + j);
+          if (rnd) tile[lane * 17 + j] = x;
+        }
+        if (!rnd) continue;
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int t = 0; t < 16; t++) {
+          const int st = 4 * t + (lane >> 4), i = i0 + (lane & 15);
+          if (se[t] != ~0u && i < MXA_MT_N && (!(se[t] & 1u) || mt_head_word(i, HW)))
+            this->rng_key((int)(se[t] >> 1))[i] = tile[st * 17 + (lane & 15)];
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+    } else if (lane < cnt) {
+      u32* key = this->rng_key((int)(ent >> 1));
+      u32 x = key[0];
+      for (int i = 1; i < last; i++) {
+        x = 1812433253u * (x ^ (x >> 30)) + (u32)i;
+        if (!(ent & 1u) || mt_head_word(i, HW)) key[i] = x;
+      }
+    }
+  }
   DEV void seed_streams(int first) {
     const MxaParams& P = E::PC;
     wfence();
     const int lane = this->lane;
+    // the seeded streams waiting for a pass, in stream order (the build's stream windows are empty
+    // here: every grs() / agent_rs() of the build starts with an empty window)
+    LDSP u32* pend = this->rwin;  // [128]
+    int np = 0;
     for (int b = first; b < P.n_streams; b += 64) {
-      int s = b + lane;
-      if constexpr (SEED_TILE) {
-        LDSP u32* tile = (LDSP u32*)this->qk;  // [64 streams][17] (16 words + a bank-conflict pad)
-        u32 x = s < P.n_streams ? this->rng_key(s)[0] : 0u;
-        for (int i0 = 1; i0 < MXA_MT_N; i0 += 16) {
-#pragma unroll
-          for (int j = 0; j < 16; j++) {
-            x = 1812433253u * (x ^ (x >> 30)) + (u32)(i0 + j);
-            tile[lane * 17 + j] = x;
-          }
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int t = 0; t < 16; t++) {  // 4 streams x 16 words per store
-            const int st = 4 * t + (lane >> 4), w = lane & 15;
-            if (b + st < P.n_streams && i0 + w < MXA_MT_N) this->rng_key(b + st)[i0 + w] = tile[st * 17 + w];
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-      } else if (s < P.n_streams) {
-        u32* key = this->rng_key(s);
-        u32 x = key[0];
-        for (int i = 1; i < MXA_MT_N; i++) {
-          x = 1812433253u * (x ^ (x >> 30)) + (u32)i;
-          key[i] = x;
-        }
+      const int s = b + lane;
+      const int cls = s < P.n_streams ? stream_cls(s) : MXA_STREAM_NONE;
+      const u64 mk = bal(cls != MXA_STREAM_NONE);
+      if (cls != MXA_STREAM_NONE)
+        pend[np + __builtin_popcountll(mk & ((1ull << lane) - 1))] = ((u32)s << 1) | (cls == MXA_STREAM_HEAD ? 1u : 0u);
+      np += __builtin_popcountll(mk);
+      __threadfence_block();
+      if (np >= 64) {
+        seed_pass(pend, 64);
+        const u32 e = pend[64 + lane];
+        __threadfence_block();
+        pend[lane] = e;
+        np -= 64;
+        __threadfence_block();
       }
     }
+    if (np > 0) seed_pass(pend, np);
     wfence();
     if constexpr (SEED_TILE) {  // the queue area again: every slot empty
       for (int j = 0; j < E::SQ; j++) this->qset(j, KEY_EMPTY, 0xFFFFFFFFu, true);
       if constexpr (E::QHIER) this->q_rescan();
     }
   }
+  // block 1's head of the agents [lo, lo + n)'s streams, MT_HEAD_BATCH per round trip
+  DEV void heads_range(int lo, int n) {
+    for (int a0 = lo; a0 < lo + n; a0 += MT_HEAD_BATCH) {
+      u32* key[MT_HEAD_BATCH];
+#pragma unroll
+      for (int q = 0; q < MT_HEAD_BATCH; q++) key[q] = this->rng_key(4 + min(a0 + q, lo + n - 1));
+      mt_gen_heads(key, min(MT_HEAD_BATCH, lo + n - a0));
+    }
+  }
 
   // rs_maint(agent stream, MXA_AGENT_LA) for every agent without a record round trip each: 64
   // records' stream position and block per load, the blocks two streams per round trip, the
-  // block numbers written back per lane (the builder's records are all in HBM: HOT is 0)
+  // block numbers written back per lane (the builder's records are all in HBM: HOT is 0).  A head
+  // stream's block 1 is its head (mt_gen_heads, a batch per round trip), a none stream's nothing:
+  // both records carry the block number they always did
   DEV void maint_agents() {
     const int n = E::PC.n_agents, lane = this->lane;
     wfence();  // the records' stores above
@@ -6074,9 +6174,22 @@ struct Builder : Eng<CFG, true> {
       u32* rw = (u32*)this->agent_ptr(act ? a : a0);
       const i32 p = act ? (i32)rw[AF_RS_POS] : 0;
       i32 m = act ? (i32)rw[AF_RS_M] : 0;
-      const i32 need = (p + MXA_AGENT_LA) / MXA_MT_N;
+      const int cls = act ? mxa_cfg::stream_class(CFG, (int)rw[AF_TYPE]) : MXA_STREAM_FULL;
+      const i32 need = (p + MXA_AGENT_LA) / MXA_MT_N;  // (1 for a head stream: its position stays inside the head)
+      for (u64 t = bal(act && cls == MXA_STREAM_HEAD && m < need); t;) {
+        u32* key[MT_HEAD_BATCH];
+        int k = 0;
+#pragma unroll
+        for (int q = 0; q < MT_HEAD_BATCH; q++) {
+          key[q] = this->rng_key(4 + a0 + (t ? ctz64(t) : 0));
+          k += t ? 1 : 0;
+          t &= t - 1;
+        }
+        mt_gen_heads(key, k);
+      }
+      if (cls != MXA_STREAM_FULL && m < need) m = need;
       for (;;) {
-        u64 t = bal(act && m < need);
+        u64 t = bal(act && cls == MXA_STREAM_FULL && m < need);
         if (!t) break;
         const int l1 = ctz64(t);
         t &= t - 1;
@@ -6566,10 +6679,24 @@ struct Builder : Eng<CFG, true> {
     this->rs64(AF_COMP, P.default_comp_delay);
     this->rec_store();
     // momentum size = A.randint(min, max); ZI theta = sorted(round(A.normal(0, sqrt(sigma_pv), 2 qmax)))
+    // (a head stream: block 1's head for all of them first, so the draw finds its block there)
+    constexpr bool MOM_HEAD = mxa_cfg::stream_class(CFG, AG_MOMENTUM) == MXA_STREAM_HEAD;
+    if constexpr (MOM_HEAD) heads_range(P.first_mom, P.n_mom);
     for (int a = P.first_mom; a < P.first_mom + P.n_mom; a++) {
       this->rec_load(a);
       ARS A = this->agent_rs();
-      this->rs(AF_SIZE, (u32)rs_randint(A, P.mom_min, P.mom_max));
+      if constexpr (MOM_HEAD) A.m = 1;
+      i64 size = rs_randint(A, P.mom_min, P.mom_max);
+      if (MOM_HEAD && MXA_UNLIKELY(A.p > MXA_MT_N + HW)) {
+        // the rejections left the head (below 2^-64 per agent): the whole stream, as a full one's,
+        // and the draw again
+        mt_seed(A.key, A.key[0]);
+        A.p = MXA_MT_N;
+        A.m = 0;
+        A.lw0 = A.lwn = 0;
+        size = rs_randint(A, P.mom_min, P.mom_max);
+      }
+      this->rs(AF_SIZE, (u32)size);
       this->agent_rs_put(A);
       this->rec_store();
     }
@@ -6606,6 +6733,10 @@ struct Builder : Eng<CFG, true> {
     }
     // run-kernel invariant: every stream has the block after its current one materialized
     for (int k = 0; k < 4; k++) {
+      if (k == 3 && L_NONE) {  // never drawn: nothing to materialise, the header reads as it did
+        h.rs_m[3] = (h.rs_pos[3] + MXA_MT_N) / MXA_MT_N;
+        continue;
+      }
       RS r = this->grs(k);
       rs_maint(r);
       this->grs_put(k, r);
@@ -6951,6 +7082,35 @@ __global__ __launch_bounds__(64) void mxa_variate_probe_kernel(uint32_t seed, co
         state[3 * k + 1] = (uint64_t)(uint32_t)r.hasg;
         state[3 * k + 2] = mxa::as_u(r.gauss);
       }
+    }
+  }
+}
+// a head stream (mxa_config.h stream classes) with a head of hw outputs: seeded and materialised by
+// the build kernel's head functions, then n randint(0, 100) draws as wake_frequency makes them (the
+// run kernel's draw from the block in HBM, then the head's guard).  state [n][2] = (p, hasg) after
+// every draw.  scratch: one stream's MT double buffer, zeroed (as the env block is)
+__global__ __launch_bounds__(64) void mxa_stream_head_probe_kernel(uint32_t seed, int hw, int n, double* out, uint64_t* state,
+                                                                   uint32_t* scratch) {
+  mxa::mt_seed_head(scratch, seed, hw);
+  uint32_t* key[MT_HEAD_BATCH];
+#pragma unroll
+  for (int q = 0; q < MT_HEAD_BATCH; q++) key[q] = scratch;
+  mxa::mt_gen_heads(key, 1, hw);
+  mxa::RSt<false> r;
+  r.lw = nullptr;  // draws read the MT block in HBM
+  r.lw0 = r.lwn = 0;
+  r.key = scratch;
+  r.p = MXA_MT_N;
+  r.m = 1;
+  r.hasg = 0;
+  r.gauss = 0;
+  for (int i = 0; i < n; i++) {
+    const double v = (double)mxa::rs_randint(r, 0, 100);
+    mxa::rs_head_guard(r, hw);
+    if (__lane_id() == 0) {
+      out[i] = v;
+      state[2 * i] = (uint64_t)(uint32_t)r.p;
+      state[2 * i + 1] = (uint64_t)(uint32_t)r.hasg;
     }
   }
 }

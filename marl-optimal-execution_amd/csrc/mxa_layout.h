@@ -56,6 +56,11 @@ enum { MT_MESSAGE = 1, MT_WAKEUP = 2, MT_CANCEL_ORDER = 3 };
 // agent classes
 enum { AG_EXCHANGE = 0, AG_ZI = 1, AG_NOISE = 2, AG_VALUE = 3, AG_POVMM = 4, AG_MOMENTUM = 5, AG_REPLAY = 6, AG_DUMMYRL = 7,
        AG_MKTMAKER = 8, AG_HBL = 9, AG_OBI = 10, AG_TWAP = 11, AG_SBMM = 12 };
+// what the build kernel materialises of an agent's own RNG stream, by its class (mxa_config.h
+// stream_class_of): both 624-word blocks, the first MXA_STREAM_HEAD_WORDS outputs of block 1 with the
+// state words A[0..HEAD_WORDS], A[397..397 + HEAD_WORDS) they are made of, or the seed word alone
+enum { MXA_STREAM_FULL = 0, MXA_STREAM_HEAD = 1, MXA_STREAM_NONE = 2 };
+#define MXA_STREAM_HEAD_WORDS 64
 // SpreadBasedMarketMakerAgent's string order ids "<name>_<id>_<n>" (generateNewOrderId,
 // SpreadBasedMarketMakerAgent.py:279-288) are carried as MXA_SB_ID_BASE + n: compared for
 // identity only, never equal to an auto id

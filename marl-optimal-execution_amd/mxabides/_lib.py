@@ -181,6 +181,10 @@ BARS_BINDINGS = {
 VARIATE_BINDINGS = {
     "mxa_variate_probe": ([_I32, _U32, _P, _I32, _I32, _P, _P], _I32),
 }
+# the export of include/mxa_streams.h (the head streams' probe; a part of mxa.h's C-ABI too)
+STREAM_BINDINGS = {
+    "mxa_stream_head_probe": ([_I32, _U32, _I32, _I32, _P, _P], _I32),
+}
 # the export of include/mxa_policy_features.h (the closed-loop step with a state of N features; a part of mxa.h's C-ABI too)
 POLICY_FEATURES_BINDINGS = {
     "mxa_step_policy_spec": ([_P, _I32, _I32, ctypes.POINTER(Policy), ctypes.POINTER(StateSpec), _P, _P, _P, _P, _P],
@@ -205,7 +209,7 @@ def load():
         raise MxaError("libmxa.so not built (%s); run __graft_entry__.build()" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in list(BINDINGS.items()) + list(SNAPSHOT_BINDINGS.items()) + list(DEPTH_BINDINGS.items()) \
-            + list(BARS_BINDINGS.items()) + list(VARIATE_BINDINGS.items()) + list(POLICY_FEATURES_BINDINGS.items()):
+            + list(BARS_BINDINGS.items()) + list(VARIATE_BINDINGS.items()) + list(STREAM_BINDINGS.items()) + list(POLICY_FEATURES_BINDINGS.items()):
         if hasattr(L, name):  # (MXA_LIB may name a variant build that lacks some)
             f = getattr(L, name)
             f.argtypes, f.restype = argtypes, restype
